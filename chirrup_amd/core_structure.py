@@ -59,7 +59,8 @@ class RequestStatus(enum.IntEnum):
 
 @dataclass
 class Task:
-    """One generation request.  ``output_queue`` receives ("token_generated", (id, text[, logits])),
+    """One generation request.  ``output_queue`` receives ("token_generated", (id, text[, logits])) -- (id, text, logits or None,
+    logprobs) when ``logprobs`` is set --
     ("cache_prefill", {"state", "prefilled_tokens"}) and ("task_completed", task) tuples;
     ``task_event_queue`` carries ("abort", payload) from the front end."""
 
@@ -85,6 +86,11 @@ class Task:
     cache_prefill: bool = False
     cache_prefill_padding: int = 0
     return_logits: bool = False
+    # log-probabilities of the raw model output (before forbidden tokens, penalties, temperature and top-p / top-k) of each
+    # generated token and of the top_logprobs (0..20) most likely ids: a fourth element {"logprob", "top_logprobs"} of the
+    # ("token_generated", ...) payload; a forbidden token can therefore appear among the top_logprobs
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -94,6 +100,8 @@ class Task:
     def __post_init__(self):
         if self.task_id is None:
             self.task_id = str(uuid.uuid4())
+        if not 0 <= self.top_logprobs <= 20 or (self.top_logprobs > 0 and not self.logprobs):
+            raise ValueError("top_logprobs must be in 0..20, and a value > 0 requires logprobs")
 
     def is_finished(self) -> bool:
         return RequestStatus.is_finished(self.request_status)

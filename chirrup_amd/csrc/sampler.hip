@@ -596,3 +596,199 @@ extern "C" int rwkv7_sample_topp(int n_rows, int V, const void *logits, const in
                        static_cast<const f16 *>(top_p), top_k, slot_idx, uniform, ids);
     return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Log-probabilities of rows of binary16 logits (token logprobs / top_logprobs of the chat API).  Per row l[0..V):
+//     m = max l,  Z = sum exp(l_i - m) in binary32,  lp(i) = (l_i - m) - log Z
+// for a per-row target id (NaN when it is outside [0, V)) and for the K <= 20 ids of largest logit, ordered by logit descending,
+// then id ascending.  One workgroup of 1024 lanes per row; the row sits in registers as packed 16-bit order-preserving keys
+// (key_of), as in sample_topp_kernel.  Every sum runs in a fixed order -- each lane over its 64 values in index order, a wave64
+// xor butterfly (commutative pairs: every lane ends with the same bits), the 16 wave sums in wave order -- so a row's outputs do
+// not depend on the launch it runs in, the rows beside it or K.
+//   K-th largest key: the two-bits-per-pass count search of the sampler's top-k (count_ge3).  Ties at that key are taken in id
+// order: each lane counts its tied entries per group of eight (16-bit counts, two groups per word), one block-wide exclusive scan
+// of the four packed words in (group, lane) order = id order gives every tied entry its rank.  The K survivors are compacted into
+// LDS (slot order arbitrary) as 32-bit composites key << 16 | (65535 - id) -- distinct, larger = earlier in the output -- and
+// ranked by one wave with K compares each.
+namespace {
+
+constexpr int kLpMaxK = 20;
+
+__global__ __launch_bounds__(kSampThreads) void token_logprobs_kernel(
+    const int V, const int K, const f16 *__restrict__ logits, const int32_t *__restrict__ rows, const int32_t *__restrict__ target_ids,
+    const int32_t *__restrict__ target_rows, float *__restrict__ out_lp, int32_t *__restrict__ out_ids) {
+    __shared__ float red[kSampThreads / 64];
+    __shared__ unsigned redn[kSampRed];
+    __shared__ unsigned scan[4 * (kSampThreads / 64)];
+    __shared__ unsigned sel[kLpMaxK];
+    __shared__ unsigned nsel;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int i = blockIdx.x;
+    const int r = rows ? rows[i] : i;
+    const f16 *src = logits + (int64_t)r * V;
+    if (tid == 0) nsel = 0;
+
+    // ---- row -> registers (group it of this lane: ids 8 (tid + 1024 it) .. + 7), max
+    constexpr int kGroups = 65536 / kSampThreads / 8;
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    unsigned kq[4 * kGroups];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int it = 0; it < kGroups; it++) {
+        const int c = 8 * (tid + it * kSampThreads);
+        if (c < V) {
+            const f16x8 v = *reinterpret_cast<const f16x8 *>(src + c);
+#pragma unroll
+            for (int e = 0; e < 8; e++) mx = fmaxf(mx, (float)v[e]);
+            const u32x4 q = __builtin_bit_cast(u32x4, v);
+#pragma unroll
+            for (int e = 0; e < 4; e++) kq[4 * it + e] = q[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) kq[4 * it + e] = 0xfc00fc00u;          // -inf: exp 0
+        }
+    }
+    mx = block_reduce_max(mx, red);
+
+    // ---- Z, then the keys (0 past the row: below every threshold)
+    float z = 0.f;
+#pragma unroll
+    for (int it = 0; it < kGroups; it++) {
+        const bool in = 8 * (tid + it * kSampThreads) < V;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const unsigned d = kq[4 * it + e];
+            const f16 lo = __builtin_bit_cast(f16, (unsigned short)(d & 0xffffu)), hi = __builtin_bit_cast(f16, (unsigned short)(d >> 16));
+            z += expf((float)lo - mx);
+            z += expf((float)hi - mx);
+            kq[4 * it + e] = in ? key_of(lo) | (key_of(hi) << 16) : 0u;
+        }
+    }
+    const float lnZ = logf(block_reduce_sum(z, red));
+    float *o = out_lp + (int64_t)i * (K + 1);
+    if (tid == 0) {
+        const int t = target_ids ? target_ids[target_rows ? target_rows[i] : i] : -1;
+        o[0] = (t >= 0 && t < V) ? ((float)src[t] - mx) - lnZ : __builtin_nanf("");
+    }
+    if (K == 0) return;
+
+    // ---- k_key = the largest key with count{key >= k_key} >= K
+    unsigned k_key = 0;
+    for (int bit = 14; bit >= 0; bit -= 2) {
+        const unsigned q1 = k_key | (1u << bit), q2 = k_key | (2u << bit), q3 = k_key | (3u << bit);
+        unsigned n1 = 0, n2 = 0, n3 = 0;
+#pragma unroll
+        for (int it = 0; it < kGroups; it++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) count_ge3(kq[4 * it + e], q1, q2, q3, q1 << 16, q2 << 16, q3 << 16, n1, n2, n3);
+        }
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1)
+            n1 += __shfl_xor(n1, w, 64), n2 += __shfl_xor(n2, w, 64), n3 += __shfl_xor(n3, w, 64);
+        __syncthreads();
+        if (lane == 0) redn[wid] = n1, redn[16 + wid] = n2, redn[32 + wid] = n3;
+        __syncthreads();
+        unsigned N1 = 0, N2 = 0, N3 = 0;
+        for (int w = 0; w < kSampThreads / 64; w++) N1 += redn[w], N2 += redn[16 + w], N3 += redn[32 + w];
+        if (N3 >= (unsigned)K) k_key = q3;
+        else if (N2 >= (unsigned)K) k_key = q2;
+        else if (N1 >= (unsigned)K) k_key = q1;
+    }
+
+    // ---- G = count{key > k_key} (< K); per-group counts of the ties at k_key, packed two 16-bit counts per word
+    unsigned gt = 0, eqw[kGroups / 2] = {0, 0, 0, 0};
+#pragma unroll
+    for (int it = 0; it < kGroups; it++) {
+        unsigned eq = 0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const unsigned d = kq[4 * it + e], lo = d & 0xffffu, hi = d >> 16;
+            gt += (lo > k_key) + (hi > k_key);
+            eq += (lo == k_key) + (hi == k_key);
+        }
+        if (8 * (tid + it * kSampThreads) >= V) eq = 0;
+        eqw[it >> 1] += eq << (16 * (it & 1));
+    }
+    // inclusive wave scans of the tie words, the wave sum of gt
+    unsigned inc[kGroups / 2];
+#pragma unroll
+    for (int w = 0; w < kGroups / 2; w++) inc[w] = eqw[w];
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+#pragma unroll
+        for (int w = 0; w < kGroups / 2; w++) {
+            const unsigned t = __shfl_up(inc[w], s, 64);
+            if (lane >= s) inc[w] += t;
+        }
+    }
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) gt += __shfl_xor(gt, w, 64);
+    __syncthreads();
+    if (lane == 63) {
+#pragma unroll
+        for (int w = 0; w < kGroups / 2; w++) scan[w * 16 + wid] = inc[w];
+    }
+    if (lane == 0) redn[wid] = gt;
+    __syncthreads();
+    unsigned G = 0, base[kGroups / 2] = {0, 0, 0, 0}, tot[kGroups / 2] = {0, 0, 0, 0};
+    for (int v = 0; v < kSampThreads / 64; v++) {
+        G += redn[v];
+#pragma unroll
+        for (int w = 0; w < kGroups / 2; w++) {
+            if (v < wid) base[w] += scan[w * 16 + v];
+            tot[w] += scan[w * 16 + v];
+        }
+    }
+    const unsigned need = (unsigned)K - G;                 // ties to take, lowest ids first
+
+    // ---- compaction of the K survivors: a bit per taken entry (bit 8 it + e), then one LDS slot per bit
+    unsigned chunk = 0;                                    // ties in the groups before `it`, over all lanes
+    unsigned long long take = 0;
+#pragma unroll
+    for (int it = 0; it < kGroups; it++) {
+        const int sh = 16 * (it & 1);
+        const unsigned rank = chunk + (((base[it >> 1] + inc[it >> 1] - eqw[it >> 1]) >> sh) & 0xffffu);
+        chunk += (tot[it >> 1] >> sh) & 0xffffu;
+        unsigned gtm = 0, eqm = 0;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const unsigned key = (kq[4 * it + (e >> 1)] >> (16 * (e & 1))) & 0xffffu;
+            gtm |= (unsigned)(key > k_key) << e;
+            eqm |= (unsigned)(key == k_key) << e;
+        }
+        if (8 * (tid + it * kSampThreads) >= V) gtm = eqm = 0;
+        for (unsigned n = rank; n < need && eqm; n++) {    // this group's ties, lowest id first, while ranks < need remain
+            gtm |= eqm & (0u - eqm);
+            eqm &= eqm - 1;
+        }
+        take |= (unsigned long long)gtm << (8 * it);
+    }
+    while (take) {
+        const int b = __builtin_ctzll(take);
+        take &= take - 1;
+        const int id = 8 * (tid + (b >> 3) * kSampThreads) + (b & 7);
+        const unsigned slot = atomicAdd(&nsel, 1u);
+        if (slot < (unsigned)kLpMaxK) sel[slot] = (key_of(src[id]) << 16) | (65535u - (unsigned)id);
+    }
+    __syncthreads();
+    if (tid < K) {
+        const unsigned me = sel[tid];
+        int pos = 0;
+        for (int j = 0; j < K; j++) pos += sel[j] > me;
+        const int id = 65535 - (int)(me & 0xffffu);
+        out_ids[(int64_t)i * K + pos] = id;
+        o[1 + pos] = ((float)src[id] - mx) - lnZ;
+    }
+}
+
+}  // namespace
+
+extern "C" int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits, const int32_t *rows, const int32_t *target_ids,
+                                    const int32_t *target_rows, float *out_lp, int32_t *out_ids, void *stream) {
+    if (n_rows <= 0 || V <= 0 || (V & 7) || V > 65536 || K < 0 || K > kLpMaxK || K > V) return CHIRRUP_E_SHAPE;
+    if (!logits || !out_lp || (K > 0 && !out_ids)) return CHIRRUP_E_NULL;
+    if (reinterpret_cast<uintptr_t>(logits) & 15) return CHIRRUP_E_ALIGN;
+    hipLaunchKernelGGL(token_logprobs_kernel, dim3((unsigned)n_rows), dim3(kSampThreads), 0, static_cast<hipStream_t>(stream), V, K,
+                       static_cast<const f16 *>(logits), rows, target_ids, target_rows, out_lp, out_ids);
+    return (int)hipGetLastError();
+}

@@ -31,7 +31,7 @@ from .remote_arena import WIRE_KEY, PeerArenas, RemoteStateRef, is_wire_row
 
 _TASK_FIELDS = ("prompt_str", "prefill_tokens", "state", "task_id", "priority", "temperature", "top_p", "top_k", "presence_penalty",
                 "frequency_penalty", "penalty_decay", "max_tokens", "stop_tokens", "forbidden_tokens", "cache_prefill",
-                "cache_prefill_padding", "return_logits")
+                "cache_prefill_padding", "return_logits", "logprobs", "top_logprobs")
 _RESULT_FIELDS = ("request_status", "generated_tokens", "decoded_texts", "prefill_tokens")
 
 
@@ -83,7 +83,7 @@ class ResultSink:
                 ref.release()
             payload = {"state": [t.detach().to("cpu") for t in st], "prefilled_tokens": tuple(payload["prefilled_tokens"])}
         elif kind == "token_generated" and len(payload) > 2:
-            payload = (payload[0], payload[1], payload[2].detach().to("cpu"))
+            payload = (payload[0], payload[1], None if payload[2] is None else payload[2].detach().to("cpu")) + tuple(payload[3:])
         self._q.put((self._id, (kind, payload)))
 
 

@@ -1,7 +1,7 @@
 """Per-request handle of the engine façade (boundary B4).
 
 Same surface as the reference's chirrup/interface.py:31-142: an async iterator over
-("token", id, text[, logits]) / ("cache_prefill", {"state", "prefilled_tokens"}) events, lazily
+("token", id, text[, logits[, logprobs]]) / ("cache_prefill", {"state", "prefilled_tokens"}) events, lazily
 submitting its Task on first iteration, with ``get_full_completion()`` and ``abort()``."""
 import asyncio
 import queue
@@ -19,7 +19,8 @@ class AsyncEngineCompletion:
                  penalty_decay: float = DEFAULT_SAMPLING_CONFIG["penalty_decay"],
                  stop_tokens: Optional[List[int]] = DEFAULT_STOP_TOKENS, forbidden_tokens: Optional[List[int]] = None,
                  max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], cache_prefill: bool = False,
-                 cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None):
+                 cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None,
+                 logprobs: bool = False, top_logprobs: int = 0):
         self.task_id = task_id
         # the worker polls it for ("abort", None); a process-mode engine passes a channel that reaches the worker's process
         self.task_event_queue = task_event_queue if task_event_queue is not None else queue.Queue()
@@ -30,7 +31,7 @@ class AsyncEngineCompletion:
                          frequency_penalty=frequency_penalty, penalty_decay=penalty_decay, max_tokens=max_tokens,
                          stop_tokens=stop_tokens, forbidden_tokens=list(forbidden_tokens or []),
                          cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
-                         return_logits=return_logits)
+                         return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs)
         self._task_queue = task_queue
         self._submitted = False
         self.is_finished = False

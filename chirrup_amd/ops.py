@@ -1103,6 +1103,58 @@ def sample_topp(logits, rows, temperature, top_p, top_k, uniform, ids, slot_idx=
     _lib.check(rc, "rwkv7_sample_topp")
 
 
+TOP_LOGPROBS_MAX = 20
+
+
+def token_logprobs(logits, k: int, targets=None, rows=None, target_rows=None):
+    """Log-probabilities of rows of fp16 logits (include/chirrup_amd.h: rwkv7_token_logprobs): launch row i reads logits[rows[i]]
+    (logits[i] without rows).  Returns (lp fp32 [n, 1 + k], ids int32 [n, k]): lp[i, 0] = log_softmax(row)[targets[target_rows[i]]]
+    (targets[i] without target_rows; NaN for an id outside [0, V) or without targets), lp[i, 1 + j] that of ids[i, j], the k (0..20)
+    ids of largest logit by logit descending, then id ascending.  Tensors off the GPU take a torch computation of the same
+    definition (the worker's CPU tests); GPU tensors always take the kernel."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or not logits.is_contiguous():
+        raise _lib.ChirrupAmdError("logits: expected contiguous fp16 [B,V]")
+    B, V = logits.shape
+    k = int(k)
+    if not 0 <= k <= min(TOP_LOGPROBS_MAX, V):
+        raise _lib.ChirrupAmdError(f"k: expected 0..{min(TOP_LOGPROBS_MAX, V)}, got {k}")
+    n = rows.numel() if rows is not None else B
+    if not logits.is_cuda:
+        return _token_logprobs_torch(logits, k, targets, rows, target_rows)
+    for name, t in (("rows", rows), ("target_rows", target_rows)):
+        if t is not None:
+            _chk(t, name, torch.int32, (n,))
+    if targets is not None:
+        _chk(targets, "targets", torch.int32)
+        if target_rows is None and targets.numel() != n:
+            raise _lib.ChirrupAmdError(f"targets: expected {n} elements without target_rows, got {targets.numel()}")
+    lp = torch.empty((n, k + 1), dtype=torch.float32, device=logits.device)
+    ids = torch.empty((n, k), dtype=torch.int32, device=logits.device)
+    if n == 0:
+        return lp, ids
+    rc = _lib.load().rwkv7_token_logprobs(n, V, k, _ptr(logits), _ptr(rows), _ptr(targets), _ptr(target_rows), _ptr(lp),
+                                          _ptr(ids) if k else None, _stream())
+    _lib.check(rc, "rwkv7_token_logprobs")
+    return lp, ids
+
+
+def _token_logprobs_torch(logits, k, targets, rows, target_rows):
+    x = (logits if rows is None else logits[rows.long()]).float()
+    n, V = x.shape
+    m = x.max(dim=1, keepdim=True).values
+    lse = torch.log(torch.exp(x - m).sum(dim=1, keepdim=True))
+    lpr = (x - m) - lse
+    lp = torch.full((n, k + 1), float("nan"), dtype=torch.float32)
+    if targets is not None:
+        t = targets.long().view(-1)
+        t = t if target_rows is None else t[target_rows.long()]
+        ok = (t >= 0) & (t < V)
+        lp[ok, 0] = lpr[ok.nonzero().view(-1), t[ok]]
+    order = torch.sort(-x, dim=1, stable=True).indices[:, :k]      # logit descending, ties by id ascending
+    lp[:, 1:] = torch.gather(lpr, 1, order)
+    return lp, order.to(torch.int32)
+
+
 def lora_act_(hbuf, first_plane: int) -> None:
     """hbuf [n, rows, D] fp16, planes first_plane.. of [v, w, a, g]: tanh on w, sigmoid on g."""
     _chk16("hbuf", hbuf)

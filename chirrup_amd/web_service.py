@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 
 from fastapi import FastAPI, HTTPException
 from fastapi.responses import StreamingResponse
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS
 from .state_cache import SimpleStateCache
@@ -46,6 +46,16 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     pad_zero: bool = True
     use_state_cache: bool = True
     cache_prefill: bool = True
+    # log-probabilities of the generated tokens (of the raw model output: before penalties, temperature, top-p and forbidden
+    # tokens) and of the top_logprobs most likely ids at each position (OpenAI's choices[0].logprobs.content)
+    logprobs: bool = False
+    top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+
+    @model_validator(mode="after")
+    def _top_logprobs_needs_logprobs(self):
+        if self.top_logprobs is not None and not self.logprobs:
+            raise ValueError("top_logprobs requires logprobs")
+        return self
 
 
 def chat_prompt(messages: List[ChatMessage], model: str) -> Tuple[str, int]:
@@ -56,6 +66,16 @@ def chat_prompt(messages: List[ChatMessage], model: str) -> Tuple[str, int]:
     variant = model.split(":")
     cue, pad = ("Assistant:<think>", 3) if "thinking" in variant else (("Assistant:", 0) if "no-thinking" in variant else ("Assistant:<think>\n</think>", 7))
     return "\n\n".join(parts + [cue]), pad
+
+
+def logprob_entry(idx2token: Dict[int, bytes], tok: int, lp: Dict[str, Any]) -> Dict[str, Any]:
+    """One element of OpenAI's logprobs.content: the vocabulary entry's bytes, their UTF-8 text ("" / [] for an id the vocabulary
+    file does not define), the token's log-probability and its top alternatives."""
+    def one(i, logprob):
+        b = idx2token.get(i, b"")
+        return {"token": b.decode("utf-8", errors="backslashreplace"), "logprob": logprob, "bytes": list(b)}
+
+    return dict(one(tok, lp["logprob"]), top_logprobs=[one(i, v) for i, v in lp["top_logprobs"]])
 
 
 class ThinkSplitter:
@@ -108,6 +128,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
     models = [{"id": i, "object": "model", "created": created, "owned_by": "chirrup"}
               for i in (model_ids or ("rwkv-latest", "rwkv-latest:thinking", "rwkv-latest:no-thinking"))]
     app.state.engine, app.state.state_cache = engine, state_cache
+    idx2token = getattr(engine.tokenizer, "idx2token", {})
 
     @app.get("/health")
     async def health():
@@ -125,6 +146,8 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         waiting for the real prefix (check_and_wait_prefill) are never woken.  Here the key is the whole prefix."""
         async for ev in completion:
             if ev[0] == "token":
+                if len(ev) > 4:                                # ("token", id, text, logits or None, logprobs)
+                    yield "logprobs", logprob_entry(idx2token, ev[1], ev[4])
                 for piece, st in splitter.feed(ev[2]):
                     if st in ("content", "reasoning_content"):
                         yield st, piece
@@ -151,7 +174,8 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                                            top_p=request.top_p, max_tokens=request.max_tokens, presence_penalty=request.presence_penalty,
                                            frequency_penalty=request.frequency_penalty, penalty_decay=request.penalty_decay,
                                            stop_tokens=set(DEFAULT_STOP_TOKENS + stops),
-                                           cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad)
+                                           cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
+                                           **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}))
         except HTTPException:
             raise
         except Exception as e:                                  # noqa: BLE001 -- app.py:231
@@ -160,27 +184,39 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         splitter.feed(prompt.split("\n\n")[-1])                 # the assistant cue sets the splitter's starting part (app.py:243)
         cid, created_at = f"chatcmpl-{uuid.uuid4().hex}", int(time.time())
 
-        def chunk(delta: Dict[str, Any], finish=None) -> str:
+        def chunk(delta: Dict[str, Any], finish=None, logprobs=None) -> str:
             body = {"id": cid, "object": "chat.completion.chunk", "created": created_at, "model": request.model,
                     "choices": [{"index": 0, "delta": delta, "finish_reason": finish}]}
+            if logprobs:
+                body["choices"][0]["logprobs"] = {"content": logprobs}
             return f"data: {json.dumps(body, ensure_ascii=False)}\n\n"
 
         async def produce(q: asyncio.Queue):
             try:
-                content, reasoning = [], []
+                content, reasoning, lps, pending = [], [], [], []
                 async for st, piece in events_of(completion, splitter, tokens[:n_cached]):
+                    if st == "logprobs":                       # rides on the next chunk sent (a token may send none)
+                        lps.append(piece)
+                        pending.append(piece)
+                        continue
                     (content if st == "content" else reasoning).append(piece)
                     if request.stream:
-                        q.put_nowait(chunk({"content": piece} if st == "content" else {"content": "", "reasoning_content": piece}))
+                        q.put_nowait(chunk({"content": piece} if st == "content" else {"content": "", "reasoning_content": piece},
+                                           logprobs=pending))
+                        pending = []
                 if request.stream:
+                    if pending:
+                        q.put_nowait(chunk({"content": ""}, logprobs=pending))
                     q.put_nowait(chunk({}, "stop"))
                     q.put_nowait("data: [DONE]\n\n")
                 else:
                     n_out = len(completion.task.generated_tokens)
+                    choice = {"index": 0, "finish_reason": "stop",
+                              "message": {"role": "assistant", "content": "".join(content), "reasoning_content": "".join(reasoning)}}
+                    if request.logprobs:
+                        choice["logprobs"] = {"content": lps}
                     q.put_nowait(json.dumps({"id": cid, "object": "chat.completion", "created": created_at, "model": request.model,
-                                             "choices": [{"index": 0, "finish_reason": "stop",
-                                                          "message": {"role": "assistant", "content": "".join(content),
-                                                                      "reasoning_content": "".join(reasoning)}}],
+                                             "choices": [choice],
                                              "usage": {"prompt_tokens": len(tokens), "completion_tokens": n_out,
                                                        "total_tokens": len(tokens) + n_out}}, ensure_ascii=False))
             except Exception as e:                              # noqa: BLE001 -- reported in-band like the reference (app.py:297-301)

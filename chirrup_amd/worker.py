@@ -7,7 +7,8 @@ Keeps the reference worker's protocol and scheduling semantics (chirrup/worker.p
     single-token prefill rows share one forward per iteration (:671-742), chunked prefill of at most
     ``max_forward_seq_len_per_forward`` tokens runs every ``decode_prefill_ratio`` iterations for at
     most ``max(batch_size/8, 1)`` sequences (:143, :744-776, :854-856);
-  * messages: ("token_generated", (id, text[, logits])), ("task_completed", task),
+  * messages: ("token_generated", (id, text[, logits])) -- (id, text, logits or None, logprobs) for a request with
+    ``logprobs`` --, ("task_completed", task),
     ("cache_prefill", {"state", "prefilled_tokens"}) on the task's output queue (:422-434, :498-501,
     :556-558), (worker_id, "worker_loaded" | "worker_performance", {...}) on the worker event queue.
 
@@ -171,6 +172,7 @@ class Worker:
         self._ids_host = ([torch.zeros((n + 1,), dtype=torch.int32).pin_memory() for _ in range(2)]     # (+ 1: the launch-status word)
                           if dev.type == "cuda" else None)
         self._launches = 0
+        self._lp_host = None                          # pinned [2] x (lp, ids) of the logprob rows, allocated when a request first asks
         # the ids each slot has sampled (ops.PenaltyLists): the penalty step then touches those entries of the dense tables only
         self._pen_lists = (ops.PenaltyLists(n, V, dev) if (self._commit_kernel is not None and dev.type == "cuda" and V % 32 == 0
                                                            and self._penalize_argmax is ops.penalize_argmax) else None)
@@ -250,9 +252,10 @@ class Worker:
             td["is_prefilling"], td["state_category"] = False, StateCategory.FORWARD_ONE_DECODE
         self._maybe_cache_prefill(td, slot)
 
-    def _handle_forward_one_decode_phase(self, td, tok: int, raw_logits=None):
+    def _handle_forward_one_decode_phase(self, td, tok: int, raw_logits=None, logprobs=None):
         """One sampled token of a live request (chirrup/worker.py:503-560): stop / length checks, text, message.
-        The penalty state was already advanced on the device when the token was sampled."""
+        The penalty state was already advanced on the device when the token was sampled.  logprobs: {"logprob", "top_logprobs"}
+        of the token (requests with ``logprobs``)."""
         t: Task = td["task"]
         td["new_token"] = tok
         if tok in t.stop_tokens:
@@ -264,7 +267,10 @@ class Worker:
             text = ""
         t.generated_tokens.append(tok)
         t.decoded_texts.append(text)
-        if t.return_logits and raw_logits is not None:
+        if t.logprobs:
+            raw = raw_logits.detach().cpu() if (t.return_logits and raw_logits is not None) else None
+            t.output_queue.put_nowait(("token_generated", (tok, text, raw, logprobs)))
+        elif t.return_logits and raw_logits is not None:
             t.output_queue.put_nowait(("token_generated", (tok, text, raw_logits.detach().cpu())))
         else:
             t.output_queue.put_nowait(("token_generated", (tok, text)))
@@ -301,12 +307,19 @@ class Worker:
             # word arrives behind every step's ids, so the step that gave up is fatal BEFORE any of its tokens is sent to a client
             # (round 3 looked at a word every replay had zeroed, every 256 iterations).
             raise RuntimeError(f"a time-mix launch gave up waiting for its own workgroups (status word {host_ids[n_rows]}): results are undefined")
+        lp = rec.get("lp")
+        if lp is not None:                                  # one copy each for the logprob rows' values and top ids
+            lp_pos, lp_val, lp_ids = lp[0], lp[1].tolist(), lp[2].tolist()
         done = []
         for j, (slot, task) in enumerate(rec["rows"]):
             td = self.state_slot[slot]
             if td["task"] is not task or RequestStatus.is_finished(task.request_status):
                 continue
-            self._handle_forward_one_decode_phase(td, int(host_ids[j]), rec["raw"].get(j))
+            entry = None
+            if lp is not None and j in lp_pos:
+                v, i, k = lp_val[lp_pos[j]], lp_ids[lp_pos[j]], task.top_logprobs
+                entry = {"logprob": v[0], "top_logprobs": list(zip(i[:k], v[1:1 + k]))}
+            self._handle_forward_one_decode_phase(td, int(host_ids[j]), rec["raw"].get(j), entry)
             if RequestStatus.is_finished(task.request_status):
                 done.append(slot)
         self._process_accomplished_tasks(done)
@@ -428,6 +441,10 @@ class Worker:
         if sampled:
             rows = self._slot_tensor(sampled)
             u = torch.rand((len(sampled),), device=self.device, dtype=torch.float32)
+        lp_rows = [j for j, s in enumerate(decode_slots) if self.state_slot[s]["task"].logprobs]
+        if lp_rows:
+            lp_idx = self._slot_tensor(lp_rows)
+            lp_k = max(self.state_slot[decode_slots[j]]["task"].top_logprobs for j in lp_rows)
         tokens = []
         for j, s in enumerate(slots):
             td = self.state_slot[s]
@@ -444,6 +461,9 @@ class Worker:
         if nd == 0:
             return None
         logits = out[:nd]
+        # logprobs are those of the raw model output: the rows that ask are copied before the forbidden tokens and the penalty
+        # kernel edit `logits` in place (the graph's output buffer is static)
+        snap = logits.index_select(0, lp_idx) if lp_rows else None
         raw = {}
         for j, s in enumerate(decode_slots):
             t: Task = self.state_slot[s]["task"]
@@ -473,6 +493,10 @@ class Worker:
                 ids[lrows] = sample_logits_rwkv_pip_compatible(logits[lrows], self.temperature_tensor[srows],
                                                                self.top_p_tensor[srows], self.top_k_tensor[srows]).to(torch.int32)
         self._commit_sampled(ids, didx, status_out)
+        lp = None
+        if lp_rows:                                         # the sampled ids are read on the device, in place
+            lp_val, lp_ids = ops.token_logprobs(snap, lp_k, targets=ids, target_rows=lp_idx)
+            lp = [{j: p for p, j in enumerate(lp_rows)}, lp_val, lp_ids]
         event = None
         if self._ids_host is not None:
             host = self._ids_host[self._launches & 1]
@@ -480,11 +504,23 @@ class Worker:
                 host[:nd + 1].copy_(buf, non_blocking=True)
             else:
                 host[:nd].copy_(ids, non_blocking=True)
+            if lp is not None:                              # double-buffered like the ids: the loop runs one forward ahead
+                if self._lp_host is None:
+                    n_max, k_max = self.real_state_size, ops.TOP_LOGPROBS_MAX
+                    self._lp_host = [(torch.empty((n_max * (k_max + 1),), dtype=torch.float32).pin_memory(),
+                                      torch.empty((n_max * k_max,), dtype=torch.int32).pin_memory()) for _ in range(2)]
+                hv, hi = self._lp_host[self._launches & 1]
+                n_lp = len(lp_rows)
+                lp[1] = hv[:lp_val.numel()].view(n_lp, lp_k + 1).copy_(lp_val, non_blocking=True)
+                lp[2] = hi[:lp_ids.numel()].view(n_lp, lp_k).copy_(lp_ids, non_blocking=True)
             event = torch.cuda.Event()
             event.record()
             ids = host
-        return {"rows": [(s, self.state_slot[s]["task"]) for s in decode_slots], "ids": ids, "event": event, "raw": raw,
-                "status": status_out is not None and self._ids_host is not None}
+        rec = {"rows": [(s, self.state_slot[s]["task"]) for s in decode_slots], "ids": ids, "event": event, "raw": raw,
+               "status": status_out is not None and self._ids_host is not None}
+        if lp is not None:
+            rec["lp"] = lp
+        return rec
 
     def _graph_for(self, n: int):
         """Smallest captured bucket >= n (buckets: powers of two up to the slot count)."""

@@ -481,6 +481,18 @@ int rwkv7_sample_topp(int n_rows, int V, const void *logits, const int32_t *rows
                       int32_t *ids, void *stream);
 
 /*
+ * Log-probabilities of n_rows rows of binary16 logits (V <= 65536, V % 8 == 0): launch row i reads logits row rows[i] (or i).
+ * m = max l, Z = sum exp(l - m) in binary32 in a fixed order, lp(j) = (l_j - m) - log Z.  out_lp binary32 [n_rows][K + 1]:
+ * out_lp[i][0] = lp of the target id target_ids[target_rows[i]] (target_ids[i] without target_rows; NaN when the id is outside
+ * [0, V) or target_ids is NULL), out_lp[i][1 + k] = lp of out_ids[i][k] (int32 [n_rows][K]): the K (0..20, K <= V) ids of largest
+ * logit, by logit descending then id ascending.  A row's outputs are bit-identical in every launch, whatever rows share it and
+ * whatever K (a smaller K gives a prefix of the entries).  The target ids are read on the device: the sampler's ids buffer of the
+ * same stream, with no host round trip.
+ */
+int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits, const int32_t *rows, const int32_t *target_ids,
+                         const int32_t *target_rows, float *out_lp, int32_t *out_ids, void *stream);
+
+/*
  * The pieces of mm8t_seq for a decode step that folds the mm8 prologue / reduce launches into the neighbouring kernels
  * (chirrup_amd/rwkv7.py, ffn_dtype = int8): LN kernel (prologue of ffn.key, rwkv7_add_ln_mix_mm8) -> mm8t_gemm_partial ->
  * mm8_reduce_rows (corrections + relu^2 of ffn.key AND the prologue of ffn.value) -> mm8t_gemm_partial -> next LN kernel
