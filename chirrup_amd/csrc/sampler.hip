@@ -549,22 +549,36 @@ __global__ __launch_bounds__(kSampThreads) void sample_topp_kernel(
     const float want = uniform[blockIdx.x] * total;
     if (tid == 0) scal[4] = -1.f;
     __syncthreads();
+    // only tokens of positive weight can be drawn: a kept token whose weight is 0 (a forbidden -inf logit kept by top_p = 1, a
+    // p^(1/T) that underflows) is stepped over -- else the walk, when its running sum never exceeds `want` by rounding, or the
+    // fall-back below would return it
     if (local > 0.f && want >= before && want < before + local) {
         float acc = before; int pick = -1;
         for (int c = c0; c < c1; c++) {
             if (key_of(row[c]) >= thr) {
-                acc += weight((float)row[c]);
-                pick = c;
-                if (acc > want) break;
+                const float wt = weight((float)row[c]);
+                if (wt > 0.f) {
+                    acc += wt;
+                    pick = c;
+                    if (acc > want) break;
+                }
             }
         }
-        scal[4] = (float)pick;           // exactly one thread's interval contains `want`
+        scal[4] = (float)pick;           // one thread's interval contains `want` (two may, by rounding: either pick is valid)
     }
     __syncthreads();
     if (tid == 0) {
         int pick = (int)scal[4];
-        if (pick < 0) {                  // want == total (u -> 1) or rounding: take the last kept token
-            for (int c = V - 1; c >= 0; c--) if (key_of(row[c]) >= thr) { pick = c; break; }
+        if (pick < 0) {                  // no interval holds `want` (u -> 1, or a rounding gap between two lanes' intervals): the
+                                         // last kept token of positive weight; the last kept token if every weight underflowed
+            int last = -1;
+            for (int c = V - 1; c >= 0; c--) {
+                if (key_of(row[c]) >= thr) {
+                    if (last < 0) last = c;
+                    if (weight((float)row[c]) > 0.f) { pick = c; break; }
+                }
+            }
+            if (pick < 0) pick = last;
         }
         ids[r] = pick;
         if (SAMP_STOP == 9) {

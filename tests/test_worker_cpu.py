@@ -222,3 +222,50 @@ def test_shutdown_event_stops_the_loop():
     mq.put({"type": "shutdown"})
     w.start()                                                              # returns instead of spinning
     assert w.shutdown_flag
+
+
+def test_host_replay_reproduces_the_workers_penalised_streams():
+    """util.replay_decode -- the reference decode-step rule restated on the host, which the GPU end-to-end tests hold the real
+    kernels to -- reproduces every id this worker emits from the raw logits it returns (return_logits=True): frequency and
+    presence penalties with and without decay, presence alone, forbidden tokens (the free-running arg-max and id 0), the
+    no-penalty ids, more requests than slots; sampled rows stay inside the replay's kept set."""
+    from util import NO_PENALTY_IDS, check_sampled_step, replay_decode
+
+    w, tq, _, _ = make_worker(batch_size=4)              # 3 usable slots: slots are reused with stale tables behind them
+    rng = np.random.default_rng(4)
+    pens = [dict(frequency_penalty=0.5, presence_penalty=0.5, penalty_decay=0.996), dict(frequency_penalty=1.0, penalty_decay=0.9),
+            dict(presence_penalty=0.8), dict(frequency_penalty=0.25, presence_penalty=2.0, penalty_decay=0.98)]
+    tasks = []
+    for i in range(9):
+        p = rng.integers(1, V, 1 + i * 3).tolist()
+        kw = dict(pens[i % 4], max_tokens=30, return_logits=True)
+        if i % 3 == 1:
+            kw["forbidden_tokens"] = [0, expected_stream(p, 1)[0]]
+        if i == 5:
+            kw.update(temperature=1.0, top_p=0.3)
+        t = new_task(p, **kw)
+        t._prompt = p
+        tasks.append(t)
+    for t in tasks[:2]:
+        tq.put(t)
+    for t in tasks[2:]:                                   # staggered arrivals
+        for _ in range(5):
+            w.step()
+        tq.put(t)
+    run_until_idle(w)
+    changed = no_pen = 0
+    for t in tasks:
+        items = [p for kind, p in t.output_queue.items if kind == "token_generated"]
+        got, raw = [p[0] for p in items], [p[2].numpy() for p in items]
+        assert len(got) == 30
+        greedy = t.temperature == 0
+        ids, pen = replay_decode(raw, got, t.frequency_penalty, t.presence_penalty, t.penalty_decay, t.forbidden_tokens, greedy=greedy)
+        if greedy:
+            assert got == ids, (t._prompt, got, ids)
+            changed += got != expected_stream(t._prompt, 30)
+        else:
+            for k, tok in enumerate(got):
+                assert check_sampled_step(pen[k], tok, t.top_p, t.top_k, t.forbidden_tokens) is None, k
+        assert not set(got) & set(t.forbidden_tokens)
+        no_pen += len(set(got) & NO_PENALTY_IDS)
+    assert changed >= 4 and no_pen > 0                    # the penalties changed streams; the no-penalty ids were met

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import rwkv7_np as M
-from util import bits
+from util import bits, kept_sets
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -161,7 +161,7 @@ def test_worker_end_to_end_matches_unbatched_greedy(run_ahead):
 
 
 @pytest.mark.parametrize("V,temp,top_p,top_k", [(1024, 1.0, 0.3, 0), (1024, 1.0, 0.9, 0), (4096, 1.5, 1.0, 5), (65536, 0.7, 0.8, 10),
-                                                (1024, 1.0, 0.0, 0), (1024, 1.0, 1.0, 1)])
+                                                (65536, 0.5, 1.0, 0), (1024, 1.0, 0.0, 0), (1024, 1.0, 1.0, 1)])
 def test_sample_topp_distribution(V, temp, top_p, top_k):
     """The sort-free sampler draws from the distribution the reference's algorithm defines
     (softmax -> top-p cutoff by value -> top-k -> p**(1/T)); frequencies over 20 000 draws match it to
@@ -183,31 +183,25 @@ def test_sample_topp_distribution(V, temp, top_p, top_k):
     if temp != 1.0:
         q = q ** (1.0 / temp)
     q = q / q.sum()
-    rows = torch.zeros(N, dtype=torch.int32, device="cuda")
     u = torch.rand(N, device="cuda")
     t = torch.full((1,), temp, dtype=torch.float16, device="cuda")
     tp = torch.full((1,), top_p, dtype=torch.float16, device="cuda")
     tk = torch.full((1,), top_k, dtype=torch.int32, device="cuda")
-    # N blocks on the same row, each with its own uniform; every block writes ids[0] -> give each its own row
-    big = logits.expand(N, V).contiguous() if V <= 4096 else None
-    if big is not None:
-        rows = torch.arange(N, dtype=torch.int32, device="cuda")
-        ids = torch.full((N,), -1, dtype=torch.int32, device="cuda")
-        ops.sample_topp(big, rows, t.expand(N).contiguous(), tp.expand(N).contiguous(), tk.expand(N).contiguous(), u, ids)
-        draws = ids.cpu().long()
-    else:
-        draws = []
-        ids = torch.full((1,), -1, dtype=torch.int32, device="cuda")
-        for i in range(400):
-            ops.sample_topp(logits, rows[:1], t, tp, tk, u[i:i + 1], ids)
-            draws.append(int(ids[0]))
-        draws = torch.tensor(draws)
-        N = 400
-    assert int(draws.min()) >= 0
+    # every block writes ids[its row] -> one row per draw, each with its own uniform; launched in batches of at most 2 000 rows
+    # (256 MB of logits at V = 65 536)
+    nb = min(N, max(1, (256 << 20) // (2 * V)), 2000)
+    draws = []
+    for s in range(0, N, nb):
+        n = min(nb, N - s)
+        ids = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        ops.sample_topp(logits.expand(n, V).contiguous(), torch.arange(n, dtype=torch.int32, device="cuda"), t.expand(n).contiguous(),
+                        tp.expand(n).contiguous(), tk.expand(n).contiguous(), u[s:s + n], ids)
+        draws.append(ids.cpu().long())
+    draws = torch.cat(draws)
+    assert draws.numel() == N and int(draws.min()) >= 0
     freq = torch.bincount(draws, minlength=V).float() / N
     assert float(freq[q == 0].sum()) == 0.0
-    if N >= 20000:
-        assert float((freq - q).abs().max()) <= 0.02
+    assert float((freq - q).abs().max()) <= 0.02
     if top_p == 0.0 or top_k == 1:
         assert bool((draws == int(p.argmax())).all())
 
@@ -229,20 +223,8 @@ def test_sample_topp_kept_set_and_the_ends_of_the_walk(V):
     logits[:, -8:] -= 30.0
     logits = logits.half().cuda()
     prob = torch.softmax(logits.float(), -1).cpu()
-    kept = []                             # per row: the kept sets for the crossing index and its two neighbours (the kernel adds the
-    for i in range(n):                    # same masses in another order: a crossing within ~1e-5 of top_p may fall one token either way)
-        sp, _ = torch.sort(prob[i], descending=True)
-        cs = torch.cumsum(sp, 0)
-        tpv = float(torch.tensor(top_p[i]).half())
-        j = min(int(torch.searchsorted(cs, torch.tensor(tpv))), V - 1)
-        near = [j] + [jj for jj in (j - 1, j + 1) if 0 <= jj < V and min(abs(float(cs[max(jj, j) - 1]) - tpv), abs(float(cs[min(jj, j)]) - tpv)) < 1e-5]
-        sets = []
-        for jj in near:
-            keep = prob[i] >= sp[jj]
-            if top_k[i] > 0:
-                keep &= prob[i] >= sp[top_k[i] - 1]
-            sets.append(keep)
-        kept.append(sets)
+    # per row: the kept sets for the crossing index and its admissible neighbours (util.kept_sets)
+    kept = [kept_sets(prob[i], top_p[i], top_k[i]) for i in range(n)]
     # slots in a permuted order, rows listed out of order
     slot_idx = torch.tensor([4, 2, 5, 0, 1, 3], dtype=torch.int32, device="cuda")
     t = torch.ones(n, dtype=torch.float16, device="cuda")

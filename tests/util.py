@@ -115,3 +115,82 @@ def check_bar(case, name, stats, bar, key="rel_linf"):
     bar = tight_bar(case, name, bar)
     record_parity(case, tensor=name, bar=bar, bar_on=key, **stats)
     assert stats[key] <= bar, (case, name, key, stats[key], bar)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# Host replay of the reference worker's decode step (chirrup/worker.py:720-728 and :527-547), which the worker end-to-end tests
+# hold the real kernels to.
+
+NO_PENALTY_IDS = frozenset({10, 33, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58})     # occurrence is not incremented for these ids
+
+
+def kept_sets(prob, top_p, top_k):
+    """The kept sets of the reference's top-p / top-k rule for one row of probabilities (float32, CPU;
+    chirrup/utils/samplers.py:171-255): cutoff by value at the first index where the descending cumulative sum reaches
+    fp16(top_p), ties at the cutoff kept; then top-k, ties at the k-th value kept.  A kernel adds the same masses in another
+    order, so where the cumulative sum crosses top_p within 1e-5 the crossing may fall one token either way: one bool mask per
+    admissible crossing index, the exact crossing first."""
+    import torch
+
+    V = prob.numel()
+    sp, _ = torch.sort(prob, descending=True)
+    cs = torch.cumsum(sp, 0)
+    tpv = float(torch.tensor(top_p).half())
+    j = min(int(torch.searchsorted(cs, torch.tensor(tpv))), V - 1)
+    near = [j] + [jj for jj in (j - 1, j + 1) if 0 <= jj < V and min(abs(float(cs[max(jj, j) - 1]) - tpv), abs(float(cs[min(jj, j)]) - tpv)) < 1e-5]
+    sets = []
+    for jj in near:
+        keep = prob >= sp[jj]
+        if top_k > 0:
+            keep &= prob >= sp[top_k - 1]
+        sets.append(keep)
+    return sets
+
+
+def replay_decode(raw_logits, emitted, frequency_penalty, presence_penalty, penalty_decay, forbidden_tokens=(),
+                  no_penalty_ids=NO_PENALTY_IDS, greedy=True):
+    """Replays one request's decode steps on the host from the raw fp16 logits of each step (Task(return_logits=True): the
+    model output before any edit) and the ids it emitted.  Per step:
+      1. forbidden ids -> -inf (what `fp16 -= 1e10` gives);
+      2. occurrence *= decay (fp32 * fp16 -> fp32);
+      3. logits = fp16(float(logits) - (alpha + occurrence * freq))   (oracle.rwkv7_np.apply_penalties);
+      4. greedy rows: the arg-max, lowest id on ties;
+      5. with the emitted id: occurrence[id] += 0 for the no-penalty ids else 1, alpha[id] = presence.
+    Returns (ids, penalised): the replay's greedy id per step (None for sampled rows) and the penalised fp16 logits per step
+    (what a sampled row draws from)."""
+    from oracle import rwkv7_np as M
+
+    f16, f32 = np.float16, np.float32
+    V = len(raw_logits[0])
+    occ, alpha = np.zeros(V, f32), np.zeros(V, f32)
+    decay, freq, pres = f16(penalty_decay), f16(frequency_penalty), f32(presence_penalty)
+    forbidden = sorted(set(int(t) for t in forbidden_tokens))
+    ids, penalised = [], []
+    for raw, tok in zip(raw_logits, emitted):
+        lg = np.array(raw, dtype=f16).reshape(V)
+        if forbidden:
+            with np.errstate(over="ignore"):
+                lg[forbidden] = (lg[forbidden].astype(f32) - f32(1e10)).astype(f16)
+        lg, occ = M.apply_penalties(lg, occ, alpha, decay, freq)
+        penalised.append(lg)
+        ids.append(int(M.greedy_sample(lg)) if greedy else None)
+        tok = int(tok)
+        occ[tok] += f32(0.0 if tok in no_penalty_ids else 1.0)
+        alpha[tok] = pres
+    return ids, penalised
+
+
+def check_sampled_step(penalised, tok, top_p, top_k, forbidden_tokens=()):
+    """A sampled row's id at one step: not forbidden, a finite penalised logit, inside one of the kept sets of the penalised
+    logits (kept_sets).  Returns a description of the failure, or None."""
+    import torch
+
+    tok = int(tok)
+    if tok in set(int(t) for t in forbidden_tokens):
+        return f"forbidden id {tok}"
+    if not 0 <= tok < len(penalised) or not np.isfinite(float(penalised[tok])):
+        return f"id {tok} has no finite logit"
+    prob = torch.softmax(torch.from_numpy(penalised.astype(np.float32)), -1)
+    if not any(bool(k[tok]) for k in kept_sets(prob, top_p, top_k)):
+        return f"id {tok} is outside the kept set (top_p {top_p}, top_k {top_k})"
+    return None
