@@ -24,16 +24,15 @@ TorchScript module: the per-layer work is organised around the HIP kernels of th
     head                                       ->  the ring GEMM (unsplit, fp16 epilogue)
 
 (that is the decode regime, 1..256 token rows; prefill chunks of more rows run the projections as library GEMMs with
-the LoRA chain beside R/K/V on a side stream)
-
+the LoRA chain beside R/K/V on a side stream).  Which form each stage takes is decided once per forward, on the host
+alone, by ``plan_forward``; ``_forward_embedded_fused`` runs that plan as a loop over the layers of the stage methods,
 and the whole decode step can be captured in a HIP graph (`capture_decode_graph`).  With
 ``fused=False`` the same arithmetic runs as plain torch ops (one rounding to fp16 per op, exactly
 the reference's eager semantics); that path exists for parity tests and for CPU host-logic tests
 and still calls the HIP WKV7 kernel on GPU -- there is no CPU fallback in the product.
 """
-import os
 import types
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -147,6 +146,11 @@ class _Layer:
         self.f_V_t = ops.tile_weight(self.f_V.t()) if (self.f_V is not None and ok(self.f_V.t())) else None
         self.lora2_t = ops.tile_weight_batch(self.lora2) if ok(self.lora2[0]) else None      # +8 * C * Dmax B per layer
 
+    def ring(self, name: str):
+        """The ring GEMM's operand `name` (rkv, O, f_K, f_V, lora2): the tile image if present, else the row-major tensor."""
+        t = getattr(self, name + "_t")
+        return t if t is not None else self.f_V.t() if name == "f_V" else getattr(self, name)     # (ffn.value: its [C, 4C] form)
+
     def quantize_ffn(self, z, i, tile: bool = False):
         """mm8 (w8a16) channel-mix: quantise ffn.key / ffn.value like the reference's quantize_weight
         (scripts/test_mm8/benchmark.py:54-85, matrices named at :447-452) and drop the fp16 copies.
@@ -209,14 +213,67 @@ class _LazyWeights(dict):
     def __contains__(self, key):
         return dict.__contains__(self, key) or key in self._lazy
 
-    def get_resident(self, key):
-        return dict.get(self, key)
-
     def keys(self):
         return list(dict.keys(self)) + list(self._lazy.keys())
 
 
-_TORCH_CARRY = bool(os.environ.get("CHIRRUP_TORCH_CARRY"))
+# Library-GEMM forms of a forward of more than 256 token rows
+_SPLIT_ROWS_MIN = 1024      # from this many rows R/K/V as three GEMMs (1.15 PFLOP/s) instead of one batched launch (1.0)
+_TUNE_MM_MIN_ROWS = 512     # from this many rows _mm_nt measures its formulation (below: the single call always won the sweep)
+
+
+class _Plan(NamedTuple):
+    """What one fused forward runs, decided once per forward by plan_forward (host only, no device needed)."""
+    hw: bool                    # decode-batch regime (<= 256 rows): the time-mix projections through the hand-written MFMA GEMMs
+    use_parts: bool             # ... and the binary16 FFN matrices too (the mm8 FFN has its own kernels)
+    fuse_core: bool             # gating + WKV7 + output chain in one kernel (else mid + scan + post launches)
+    row_halves: Dict[str, bool]
+    rkv: str                    # R/K/V: chain_mm8 | chain | grouped | mm8 (one at a time) | skinny_bmm | mm3 | bmm
+    lora: str                   # LoRA chain: launch (in the R/K/V launch) | grouped | per_problem | bmm_ring | bmm_baddbmm
+    side: bool                  # the LoRA chain on the side stream, beside R/K/V on this one
+    att_out: str                # att.output: mm8_fused (prologue from the core) | mm8 | ring (partials into LN2) | library
+    ffn_key: str                # mm8_fused | mm8_pair | mm8_partial (+ reduce) | mm8_dequant | mm8 | ring (+ relu^2) | mm_nt
+    ffn_value: str              # mm8_parts (into the next LN) | mm8_dequant | mm8 | sparse | ring (partials) | mm_nt | matmul
+    head: str                   # mm8 | ring | library
+
+
+def plan_forward(knobs, rows: int, T: int, C: int, layer) -> _Plan:
+    """The dispatch of a fused forward over `rows` = B * T token rows of width C.  `knobs`: anything with RWKV_x070's knob
+    attributes; `layer`: anything with _Layer's tiling facts (a8_tiled, f8_tiled, rkv_t, lora2_t, f_V_rows).  Host only."""
+    gs, a8, f8 = knobs.gemm_splits, knobs.att_dtype == torch.int8, knobs.ffn_dtype == torch.int8
+    hw = knobs.skinny_ffn_value and knobs.skinny_min_rows <= rows <= 256 and C >= knobs.skinny_min_embd
+    use_parts = hw and not f8
+    # chunks of many tokens: gating, decay and group norm in row-parallel launches around a recurrence-only scan
+    fuse_core = knobs.fuse_tmix_core and not (knobs.split_tmix_min_T and T >= knobs.split_tmix_min_T)
+    rh = knobs.gemm_row_halves if rows >= knobs.row_halves_min_rows else dict.fromkeys(knobs.gemm_row_halves, False)
+    grouped = hw and knobs.group_tmix_gemms
+    one_launch = grouped and knobs.chain_tmix_gemms and (rh["rkv"] or rows <= 128) and layer.lora2_t is not None
+    rkv = ("chain_mm8" if a8 and one_launch and T == 1 and layer.a8_tiled else
+           "chain" if not a8 and one_launch and ops.TMIX_CHAIN and rows >= knobs.chain_min_rows and layer.rkv_t is not None and not gs["rkv"] else
+           "mm8" if a8 else "grouped" if grouped else "skinny_bmm" if hw and knobs.skinny_rkv else "mm3" if rows >= _SPLIT_ROWS_MIN else "bmm")
+    # (bmm_ring: pack_for_fused pads the LoRA ranks to whole 64-wide K-blocks, which the ring kernel needs)
+    lora = ("launch" if rkv in ("chain_mm8", "chain") else "grouped" if grouped else "per_problem" if not hw else
+            "bmm_ring" if knobs.skinny_lora_up else "bmm_baddbmm")
+    att_out = (("mm8_fused" if hw and T == 1 and fuse_core and knobs.skinny_att_out else "mm8") if a8 else
+               "ring" if hw and knobs.skinny_att_out and rows >= knobs.skinny_wide_rows else "library")
+    if f8 and hw and T == 1:
+        # ffn.key's corrections + relu^2 + ffn.value's prologue in the key GEMM's epilogue (unsplit launch, row halves); few rows:
+        # the key product split over K and reduced by each tile's last workgroup, with the same epilogue -- no reduce launch
+        ffn_key, ffn_value = "mm8_partial", "mm8_parts"
+        if knobs.mm8_fused_key and rows >= knobs.row_halves_min_rows and 4 * C < 32768:
+            ffn_key = "mm8_fused"
+        elif (knobs.mm8_fused_key and knobs.mm8_pair_key and rows <= knobs.mm8_pair_max_rows and layer.f8_tiled
+              and ops.mm8_fused_split_ok(rows, C, 4 * C, gs["ffn_key"])):
+            ffn_key = "mm8_pair"
+    elif f8:
+        ffn_key = ffn_value = "mm8_dequant" if rows > 256 and knobs.mm8_prefill_dequant else "mm8"
+    else:
+        ffn_key = "ring" if use_parts and knobs.skinny_ffn_key and rows >= knobs.skinny_wide_rows else "mm_nt"
+        # (mm_nt: ffn.value's [C, 4C] Linear weight is contiguous, as convert_checkpoint and _row_major lay it out: the NT form)
+        ffn_value = ("sparse" if rows == 1 and layer.f_V_rows is not None else "ring" if use_parts else
+                     "mm_nt" if rows >= _TUNE_MM_MIN_ROWS else "matmul")
+    head = "mm8" if a8 else "ring" if (hw or not knobs.keep_row_major) and knobs.skinny_head and rows // T <= 256 else "library"
+    return _Plan(hw, use_parts, fuse_core, rh, rkv, lora, lora not in ("launch", "grouped"), att_out, ffn_key, ffn_value, head)
 
 
 def lib_cu_count() -> int:
@@ -262,7 +319,6 @@ class RWKV_x070:
         # on a side stream, forked and joined with events (capturable in the decode graph)
         # (a high-priority side stream was tried for the LoRA chain: the captured step went 8.4 -> 14.1 ms)
         self._side = torch.cuda.Stream(device=self.device) if (fused and self.device.type == "cuda") else None
-        self.overlap_lora = True
         self.fuse_tmix_core = wkv_impl is None           # one kernel for gating + WKV7 + output chain
         self.split_tmix_min_T = 32                       # ... up to this many tokens per sequence; longer chunks: row-parallel gating / decay /
                                                          # group-norm launches around a recurrence-only scan (0: never)
@@ -271,16 +327,13 @@ class RWKV_x070:
         self.skinny_min_embd = skinny_min_embd           # ... at every model size (1.5B bsz 32: -26 %, 0.1B bsz 1: -34 % vs the library)
         self.skinny_lora_up = True                       # LoRA up-projections (+bias in the epilogue) as one batched launch of the same kernel
         self.tune_prefill_gemms = True                   # library GEMMs of a chunked-prefill forward: whole or as two row halves, measured once per shape (_mm_nt)
-        self.tune_mm_min_rows = 512                      # (below: the single call always won the sweep)
         self._mm_plan: Dict[tuple, str] = {}
         self.mm8_prefill_dequant = True                  # uint8 ffn above 256 rows: dequantise into a binary16 scratch + library GEMM (False: 256-row blocks through the ring kernel)
         self.mm8_fused_key = True                        # mm8 ffn.key: corrections, relu^2 and ffn.value's prologue in the GEMM epilogue (>= 128 rows)
         self.mm8_pair_key = True                         # ... and at few rows: the K split reduced inside the launch, the same epilogue (no mm8_reduce_rows launch)
         self.mm8_pair_max_rows = 16                      # A/B on one box (profiles/r03_mm8_pair_key.txt): 7.2B bsz 8 3.11 -> 3.07 ms; bsz 32 3.37 -> 3.38, 1.5B bsz 32 1.687 -> 1.70,
                                                          # 13.3B bsz 64 +-0 -- the last arriver's epilogue costs what the reduce launch cost
-        self.split_rows_min = 1024                       # library GEMMs from this many rows: ffn.key as two row halves, R/K/V as three launches
-        self.lora_per_problem = True                     # above 256 rows: one library GEMM per LoRA at its own rank, bias in the epilogue
-        self.lora_up_row_halves = True                      # ... two row halves per tile: 256 workgroups and a deeper operand ring
+        self.lora_up_row_halves = True                   # LoRA up-projections of the decode regime: two row halves per tile, 256 workgroups and a deeper operand ring
         self.group_tmix_gemms = True                     # R/K/V + LoRA down-projections (+ activations) as ONE grouped launch, no side stream
         self.chain_tmix_gemms = True                     # ... and the LoRA up-projections in that SAME launch, on the CUs R/K/V leaves idle
         if self.fused:
@@ -336,6 +389,8 @@ class RWKV_x070:
                     lw.tile_for_ring()
                 if att_dtype == torch.int8:
                     _quantize_att(lw, self.z, i, tile=self.tiled_weights)
+            facts = {(lw.a8_tiled, getattr(lw, "f8_tiled", False), lw.rkv_t is None, lw.lora2_t is None, lw.f_V_rows is None) for lw in self._layers}
+            assert len(facts) <= 1, "plan_forward reads the tiling facts of layer 0: every layer must have the same"
             if att_dtype == torch.int8:
                 from .quant import quantize_linear
 
@@ -359,7 +414,7 @@ class RWKV_x070:
         everywhere above 256 rows."""
         rows = x2.shape[0]
         plan = "whole"
-        if rows >= self.tune_mm_min_rows and self.tune_prefill_gemms and x2.is_cuda:
+        if rows >= _TUNE_MM_MIN_ROWS and self.tune_prefill_gemms and x2.is_cuda:
             key = (rows, w.shape[0], w.shape[1])
             plan = self._mm_plan.get(key)
             if plan is None:
@@ -432,10 +487,8 @@ class RWKV_x070:
         self._scratch = None
 
     def _row_major(self, lw):
-        """(rkv [3,C,C], O [C,C], f_K [4C,C], f_V view [4C,C]) of a layer for the library GEMMs: the resident tensors, or --
-        tile-image-only model -- rebuilt into ONE scratch set that every layer reuses (stream order keeps that safe)."""
-        if lw.rkv is not None:
-            return lw.rkv, lw.O, lw.f_K, lw.f_V
+        """(rkv [3,C,C], O [C,C], f_K [4C,C], f_V view [4C,C]) of a layer of a tile-image-only model for the library GEMMs, rebuilt
+        into ONE scratch set that every layer reuses (stream order keeps that safe)."""
         C, dev = self.n_embd, self.device
         if self._scratch is None:
             new = lambda *sh: torch.empty(sh, dtype=DTYPE, device=dev)
@@ -447,10 +500,6 @@ class RWKV_x070:
         ops.untile_weight(lw.f_K_t, f_K)
         ops.untile_weight(lw.f_V_t, f_Vt)
         return rkv, O, f_K, f_Vt.t()
-
-    def _head_row_major(self):
-        hw = self.z.get_resident("head.weight") if isinstance(self.z, _LazyWeights) else self.z["head.weight"]
-        return hw if hw is not None else self.z["head.weight"]
 
     # ------------------------------------------------------------------ reference surface
     def generate_zero_state(self, bsz: int):
@@ -619,307 +668,249 @@ class RWKV_x070:
         return self._forward_embedded_fused(x, pool, tok.shape[1], full_output, slot_idx=slot_idx, elapsed_rows=elapsed_rows)
 
     def _forward_embedded_fused(self, x, state, T, full_output, slot_idx=None, elapsed_rows=None):
-        """Same arithmetic as _forward_embedded with every element-wise chain in one HIP kernel
-        (csrc/elementwise.hip, csrc/wkv7.hip) and, in the decode-batch regime (`hw` below), every projection of the
-        layer through the MFMA ring GEMM (csrc/skinny_gemm.hip).  x [B,T,C] is consumed (updated in place as the
-        residual stream)."""
-        z = self.z
+        """_forward_embedded's arithmetic as plan_forward dispatches it: every element-wise chain in one HIP kernel (csrc/elementwise.hip,
+        csrc/wkv7.hip), in the decode regime every projection through the MFMA ring GEMM (csrc/skinny_gemm.hip).  x [B,T,C] is consumed."""
         s0, s1, s2 = state
-        if slot_idx is not None:
-            # (the slots' step counters come in batch-row order from the embedding launch when it ran, ops.embed_rows)
-            elapsed = elapsed_rows if elapsed_rows is not None else s2.index_select(0, slot_idx.long())
-        else:
-            elapsed = s2
+        # (the slots' step counters come in batch-row order from the embedding launch when it ran, ops.embed_rows)
+        elapsed = s2 if slot_idx is None else elapsed_rows if elapsed_rows is not None else s2.index_select(0, slot_idx.long())
+        if not all(s0[i][j].is_contiguous() and s1[i].is_contiguous() for i in range(len(self._layers)) for j in (0, 1)):
+            raise ops._lib.ChirrupAmdError("state[0][layer][j] and state[1][layer] views must be contiguous (slice the batch dim only)")
         B, _, C = x.shape
-        H, rows, dev = self.n_head, B * T, x.device
-        x = x.contiguous()
+        p = plan_forward(self, B * T, T, C, self._layers[0])
+        f = self._fused_buffers(p, x.contiguous(), T, s0, slot_idx, elapsed)
+        for i, lw in enumerate(self._layers):
+            # library-GEMM operands (more than 256 rows): resident, or rebuilt from the tile images (keep_row_major=False)
+            w_rkv, w_O, w_fK, w_fV = (lw.rkv, lw.O, lw.f_K, lw.f_V) if p.hw or self.keep_row_major else self._row_major(lw)
+            self._add_ln(f, lw.ln1_w, lw.ln1_b, s0[i][0], lw.mix6, f.mixed, f.delta, f.dparts, f.dq,
+                         (lw.rkv8_ry, lw.rkv8_my, f.xs_rkv, f.S_rkv) if p.rkv == "chain_mm8" else None)
+            rkv, up = self._rkv_lora(p, f, i, lw, w_rkv)
+            self._tmix_core(p, f, i, lw, rkv, up, s1[i])
+            self._att_output(p, f, lw, s0[i][1], w_O)
+            self._channel_mix(p, f, lw, w_fK, w_fV)
+        return self._ln_out_head(p, f, full_output, s2)
+
+    def _fused_buffers(self, p: _Plan, x, T, s0, slot_idx, elapsed):
+        """Per-forward buffers, and what the layer loop carries between stages: the residual stream x, the previous channel-mix's
+        output (delta, or split-K partials dparts + the mm8 corrections dq), v_first."""
+        B, _, C = x.shape
+        rows, dev, gs = B * T, x.device, self.gemm_splits
         new = lambda *shape: torch.empty(shape, dtype=DTYPE, device=dev)
-        mixed, kin, o_in = new(6, rows, C), new(1, B, T, C), new(B, T, C)
-        # chunks of many tokens: the state-independent arithmetic (gating, decay, group norm) in row-parallel launches
-        # around a scan that keeps only the recurrence; single tokens: everything in one kernel (k', v', -kk, kk*a, y stay on chip)
-        fuse_core = self.fuse_tmix_core and not (self.split_tmix_min_T and T >= self.split_tmix_min_T)
-        if not fuse_core:
-            y, neg_kk, kka = new(B, T, C), new(B, T, C), new(B, T, C)
-        carry = (new(B, C) if slot_idx is None else torch.empty_like(s0[0][0])) if T > 1 else None
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        f = types.SimpleNamespace(B=B, T=T, C=C, rows=rows, new=new, x=x, slot_idx=slot_idx, elapsed=elapsed, delta=None,
+                                  dparts=None, dq=None, v_first=None)
+        f.mixed, f.kin, f.o_in = new(6, rows, C), new(1, B, T, C), new(B, T, C)
+        f.y, f.neg_kk, f.kka = (new(B, T, C), new(B, T, C), new(B, T, C)) if not p.fuse_core else (None, None, None)
+        f.carry = (new(B, C) if slot_idx is None else torch.empty_like(s0[0][0])) if T > 1 else None
         # T > 1: the LN kernel's row t re-reads x[t-1] (+ delta[t-1]) for the token shift, so the updated residual
         # stream must not be written over x while other rows of the launch still read it: ping-pong two buffers
-        x_alt = torch.empty_like(x) if T > 1 else None
-        delta, v_first = None, None
-        dparts = None                     # split-K partials of the previous ffn.value GEMM (summed by the next LN kernel)
-        # decode-batch regime of the hand-written MFMA GEMMs: time-mix projections for either FFN dtype (`hw`), the fp16
-        # FFN matrices on top of that (`use_parts`; the mm8 FFN has its own kernels)
-        hw = self.skinny_ffn_value and self.skinny_min_rows <= rows <= 256 and C >= self.skinny_min_embd
-        use_parts = hw and self.ffn_dtype == torch.float16
-        gs = self.gemm_splits
-        rh = self.gemm_row_halves if rows >= self.row_halves_min_rows else dict.fromkeys(self.gemm_row_halves, False)
-        pbuf = (torch.empty((ops.gemm_splits(C, 4 * C, 1, gs["ffn_value"]), rows, C), dtype=torch.float32, device=dev)
-                if use_parts else None)
-        pbuf_o = (torch.empty((ops.gemm_splits(C, C, 1, gs["att_out"]), rows, C), dtype=torch.float32, device=dev)
-                  if (hw and self.skinny_att_out and rows >= self.skinny_wide_rows) else None)      # (also the uint8 att.output's core partials)
+        f.x_alt = torch.empty_like(x) if T > 1 else None
+        # split-K partials of att.output (or the uint8 att.output's core partials) and of ffn.value, summed by the next LN kernel
+        f.pbuf_o = f32(ops.gemm_splits(C, C, 1, gs["att_out"]), rows, C) if p.att_out in ("ring", "mm8_fused") else None
+        f.pbuf = f32(ops.gemm_splits(C, 4 * C, 1, gs["ffn_value"]), rows, C) if p.use_parts or p.ffn_value == "mm8_parts" else None
+        f.S_o = f32(rows, self.n_head, 3) if p.att_out == "mm8_fused" else None
+        f.xs_rkv, f.S_rkv = (new(3, rows, C), f32(3, rows, 3)) if p.rkv == "chain_mm8" else (None, None)
+        if p.ffn_value == "mm8_parts":
+            # mm8 FFN in the decode regime: prologue / reduce launches of the two u8 products folded into the LN kernels and one
+            # row-reduce kernel between them (same arithmetic as ops.mm8t_linear; DESIGN.md section 5)
+            f.xs_k, f.S_k, f.xs_v = new(rows, C), f32(rows, 3), new(rows, 4 * C)
+            f.S_v = f32(rows, ops.mm8_row_parts(4 * C) if p.ffn_key == "mm8_partial" else ops.mm8_tile_parts(4 * C), 3)
+            f.pbuf_k = None if p.ffn_key == "mm8_fused" else f32(ops.gemm_splits(4 * C, C, 1, gs["ffn_key"]), rows, 4 * C)
+        return f
 
-        # mm8 FFN in the decode regime: prologue / reduce launches of the two u8 products folded into the LN kernels and one
-        # row-reduce kernel between them (same arithmetic as ops.mm8t_linear; DESIGN.md section 5)
-        q8 = hw and self.ffn_dtype == torch.int8 and T == 1
-        dq = None                         # (rx, mx, S) of the mm8 product whose core partials `dparts` holds
-        # mm8 time-mix projections (att_dtype=int8).  Decode regime: att.output's activation prologue comes out of the fused
-        # time-mix core and its corrections are applied by LN2 (like ffn.value's by LN1); everything else -- and every
-        # projection outside the decode regime -- goes through mm8t_linear (prologue, uint8 MFMA GEMM, reduce).
-        a8 = self.att_dtype == torch.int8
-        a8_out_fused = a8 and hw and T == 1 and fuse_core and self.skinny_att_out
-        S_o = torch.empty((rows, H, 3), dtype=torch.float32, device=dev) if a8_out_fused else None
-        xs_rkv = S_rkv = None
-        if q8:
-            f32 = dict(dtype=torch.float32, device=dev)
-            xs_k, S_k = new(rows, C), torch.empty((rows, 3), **f32)
-            # ffn.key's corrections + relu^2 + ffn.value's prologue in the key GEMM's epilogue (unsplit launch, row halves)
-            key_fused = self.mm8_fused_key and rows >= self.row_halves_min_rows and 4 * C < 32768
-            # few rows: the key product split over K and reduced by each tile's last workgroup, with the same epilogue -- no reduce launch
-            key_pair = (self.mm8_fused_key and self.mm8_pair_key and rows <= self.mm8_pair_max_rows and not key_fused and self._layers[0].f8_tiled
-                        and ops.mm8_fused_split_ok(rows, C, 4 * C, gs["ffn_key"]))
-            xs_v = new(rows, 4 * C)
-            S_v = torch.empty((rows, ops.mm8_tile_parts(4 * C) if (key_fused or key_pair) else ops.mm8_row_parts(4 * C), 3), **f32)
-            pbuf_k = None if key_fused else torch.empty((ops.gemm_splits(4 * C, C, 1, gs["ffn_key"]), rows, 4 * C), **f32)
-            pbuf = torch.empty((ops.gemm_splits(C, 4 * C, 1, gs["ffn_value"]), rows, C), **f32)
-
-        def commit_carry(prev):
-            if slot_idx is None:
-                prev.copy_(carry)
+    def _add_ln(self, f, ln_w, ln_b, prev, mix, out, delta, parts, mm8_in, mm8_out):
+        """Residual add (of delta, or of split-K partials) + LN + token shift + lerps in one launch; at T > 1 then the swap of the
+        residual stream's ping-pong buffers and the commit of the token-shift carry into the state."""
+        upd = delta is not None or parts is not None
+        ops.add_ln_mix(f.B, f.T, f.C, f.x, delta, (f.x if f.T == 1 else f.x_alt) if upd else None, ln_w, ln_b, 1e-5, prev,
+                       prev if f.T == 1 else f.carry, mix, out, f.slot_idx, delta_partials=parts, mm8_in=mm8_in, mm8_out=mm8_out)
+        if f.T > 1:
+            if upd:
+                f.x, f.x_alt = f.x_alt, f.x
+            if f.slot_idx is None:
+                prev.copy_(f.carry)
             else:
-                if _TORCH_CARRY:                                   # (A/B switch CHIRRUP_TORCH_CARRY=1: the torch ops this replaced)
-                    i64 = slot_idx.long()
-                    prev.index_copy_(0, i64, carry.index_select(0, i64))
-                else:
-                    ops.copy_slot_rows(carry, prev, slot_idx)      # one launch
+                ops.copy_slot_rows(f.carry, prev, f.slot_idx)      # one launch
 
-        for i, lw in enumerate(self._layers):
-            for j in (0, 1):
-                if not s0[i][j].is_contiguous():
-                    raise ops._lib.ChirrupAmdError("state[0][layer][j] view must be contiguous (slice the batch dim only)")
-            # library-GEMM operands (more than 256 rows): resident, or rebuilt from the tile images (keep_row_major=False)
-            w_rkv, w_O, w_fK, w_fV = (lw.rkv, lw.O, lw.f_K, lw.f_V) if (hw or self.keep_row_major) else self._row_major(lw)
-            # residual add of the previous channel-mix + LN1 + token shift + six lerps
-            prev = s0[i][0]
-            upd = delta is not None or dparts is not None
-            # uint8 R/K/V in the decode regime: LN1 also writes their three activation prologues, the time-mix launch multiplies
-            # them against the uint8 tiles and corrects in the tiles' epilogues (rwkv7_tmix_gemms_mm8)
-            a8_rkv_fused = (a8 and hw and T == 1 and self.group_tmix_gemms and self.chain_tmix_gemms and lw.a8_tiled
-                            and lw.lora2_t is not None and (rh["rkv"] or rows <= 128))
-            if a8_rkv_fused and xs_rkv is None:
-                xs_rkv = new(3, rows, C)
-                S_rkv = torch.empty((3, rows, 3), dtype=torch.float32, device=dev)
-            ops.add_ln_mix(B, T, C, x, delta, (x if T == 1 else x_alt) if upd else None, lw.ln1_w, lw.ln1_b,
-                           1e-5, prev, prev if T == 1 else carry, lw.mix6, mixed, slot_idx, delta_partials=dparts, mm8_in=dq,
-                           mm8_out=(lw.rkv8_ry, lw.rkv8_my, xs_rkv, S_rkv) if a8_rkv_fused else None)
-            if T > 1:
-                if upd:
-                    x, x_alt = x_alt, x
-                commit_carry(prev)
-            # planes: 0 r, 1 k, 2 v, 3 w, 4 a, 5 g
-            p0 = 1 if i == 0 else 0                                                           # layer 0 has no v gate
-            main = torch.cuda.current_stream()
-            side = self._side if self.overlap_lora else None
-            grouped = hw and self.group_tmix_gemms
-            chained = (grouped and self.chain_tmix_gemms and ops.TMIX_CHAIN and rows >= self.chain_min_rows and (rh["rkv"] or rows <= 128)
-                       and lw.lora2_t is not None and lw.rkv_t is not None and not gs["rkv"] and not a8)
-            if a8 and not a8_rkv_fused:                        # r, k, v through the uint8 weights, one product at a time
+    def _rkv_lora(self, p: _Plan, f, i, lw: _Layer, w_rkv):
+        """R/K/V of mixed[0:3] and the LoRA chain of planes (v,) w, a, g: returns rkv [3, rows, C] and up (one [rows, C] per LoRA)."""
+        rows, C, mixed, new, rh = f.rows, f.C, f.mixed, f.new, p.row_halves
+        p0 = 1 if i == 0 else 0                     # layer 0 has no v gate; planes: 0 r, 1 k, 2 v, 3 w, 4 a, 5 g
+        act = lambda j: "tanh" if j == 1 else ("sigmoid" if j == 3 else None)
+        if p.rkv == "mm8":                          # r, k, v through the uint8 weights, one product at a time
+            rkv = new(3, rows, C)
+            for j, w8 in enumerate((lw.R8, lw.K8, lw.V8)):
+                ops.mm8t_linear(mixed[j], *w8, out=rkv[j], tiled=lw.a8_tiled)
+        if p.lora == "launch":
+            # ONE launch for R/K/V AND the whole LoRA chain: down-projections, activations and up-projections run on the CUs
+            # the R/K/V tiles leave idle, beside them (chain_gemm_kernel) -- no second launch for the up-projections.  uint8
+            # R/K/V: LN1 wrote their three activation prologues, the tiles' epilogues correct (rwkv7_tmix_gemms_mm8)
+            rkv, hid, up = new(3, rows, C), new(4 - p0, rows, lw.lora1.shape[1]), new(4 - p0, rows, C)
+            main_p = ([(f.xs_rkv[j], (w8.qT, True), rkv[j], w8.rx, w8.mx, f.S_rkv[j]) for j, w8 in enumerate((lw.R8, lw.K8, lw.V8))]
+                      if p.rkv == "chain_mm8" else [(mixed[j], lw.rkv_t[j], rkv[j]) for j in range(3)])
+            lora_p = [(mixed[2 + j], lw.lora1[j, :lw.lora_k[j]], j - p0, lw.lbias[j].view(-1), up[j - p0], act(j), lw.lora_k[j])
+                      for j in range(p0, 4)]
+            ops.tmix_gemms(main_p, lora_p, lw.lora2_t[p0:], hid, row_halves=rh["rkv"], mm8=p.rkv == "chain_mm8")
+            return rkv, up
+        if not p.side:                              # (grouped)
+            # ONE launch for R/K/V and the LoRA down-projections (+ their activations in its reduce), then the
+            # LoRA up-projections, all on this stream: no cross-stream edges (they cost ~19 us per layer, DESIGN.md 5)
+            hid = new(4 - p0, rows, lw.lora1.shape[1])         # columns past a problem's rank are never read
+            if p.rkv == "grouped":
                 rkv = new(3, rows, C)
-                for j, w8 in enumerate((lw.R8, lw.K8, lw.V8)):
-                    ops.mm8t_linear(mixed[j], *w8, out=rkv[j], tiled=lw.a8_tiled)
-            if a8_rkv_fused:
-                rkv = new(3, rows, C)
-                hid = new(4 - p0, rows, lw.lora1.shape[1])
-                up = new(4 - p0, rows, C)
-                main_p = [(xs_rkv[j], (w8.qT, True), rkv[j], w8.rx, w8.mx, S_rkv[j]) for j, w8 in enumerate((lw.R8, lw.K8, lw.V8))]
-                lora_p = [(mixed[2 + j], lw.lora1[j, :lw.lora_k[j]], j - p0, lw.lbias[j].view(-1), up[j - p0],
-                           ("tanh" if j == 1 else ("sigmoid" if j == 3 else None)), lw.lora_k[j]) for j in range(p0, 4)]
-                ops.tmix_gemms(main_p, lora_p, lw.lora2_t[p0:], hid, row_halves=rh["rkv"], mm8=True)
-                side = None
-            elif chained:
-                # ONE launch for R/K/V AND the whole LoRA chain: down-projections, activations and up-projections run on the CUs
-                # the R/K/V tiles leave idle, beside them (chain_gemm_kernel) -- no second launch for the up-projections
-                rkv = new(3, rows, C)
-                hid = new(4 - p0, rows, lw.lora1.shape[1])
-                up = new(4 - p0, rows, C)
-                main_p = [(mixed[j], lw.rkv_t[j], rkv[j]) for j in range(3)]
-                lora_p = [(mixed[2 + j], lw.lora1[j, :lw.lora_k[j]], j - p0, lw.lbias[j].view(-1), up[j - p0],
-                           ("tanh" if j == 1 else ("sigmoid" if j == 3 else None)), lw.lora_k[j]) for j in range(p0, 4)]
-                ops.tmix_gemms(main_p, lora_p, lw.lora2_t[p0:], hid, row_halves=rh["rkv"])
-                side = None
-            elif grouped:
-                # ONE launch for R/K/V and the LoRA down-projections (+ their activations in its reduce), then the
-                # LoRA up-projections, all on this stream: no cross-stream edges (they cost ~19 us per layer, DESIGN.md 5)
-                hid = new(4 - p0, rows, lw.lora1.shape[1])         # columns past a problem's rank are never read
-                if a8:
-                    probs = []
-                else:
-                    rkv = new(3, rows, C)
-                    wr = lw.rkv_t if lw.rkv_t is not None else lw.rkv
-                    probs = [(mixed[j], wr[j], rkv[j], None, None) for j in range(3)]
-                for j in range(p0, 4):
-                    kj = lw.lora_k[j]
-                    probs.append((mixed[2 + j], lw.lora1[j, :kj], hid[j - p0, :, :kj], None, ("tanh" if j == 1 else ("sigmoid" if j == 3 else None))))
-                ops.skinny_group(probs, splits=gs["rkv"], row_halves=rh["rkv"])
-                # the up-projections: 4 x C/128 tiles of 2..8 K-blocks -- two row halves per tile fill the chip
-                up = ops.skinny_bmm(hid[: 4 - p0], (lw.lora2_t if lw.lora2_t is not None else lw.lora2)[p0:], lw.lbias[p0:], splits=1,
-                                    k_of=lw.lora_k[p0:], row_halves=self.lora_up_row_halves)
-                side = None
-            if side is not None:
-                side.wait_stream(main)
-            with torch.cuda.stream(side if side is not None else main):
-              if not grouped and not hw and self.lora_per_problem:
+            probs = [(mixed[j], lw.ring("rkv")[j], rkv[j], None, None) for j in range(3)] if p.rkv == "grouped" else []
+            probs += [(mixed[2 + j], lw.lora1[j, :lw.lora_k[j]], hid[j - p0, :, :lw.lora_k[j]], None, act(j)) for j in range(p0, 4)]
+            ops.skinny_group(probs, splits=self.gemm_splits["rkv"], row_halves=rh["rkv"])
+            # the up-projections: 4 x C/128 tiles of 2..8 K-blocks -- two row halves per tile fill the chip
+            up = ops.skinny_bmm(hid[: 4 - p0], lw.ring("lora2")[p0:], lw.lbias[p0:], splits=1, k_of=lw.lora_k[p0:],
+                                row_halves=self.lora_up_row_halves)
+            return rkv, up
+        main, side = torch.cuda.current_stream(), self._side
+        side.wait_stream(main)
+        with torch.cuda.stream(side):                   # the LoRA chain on the side stream, beside R/K/V on this one
+            hid, up = None, []
+            if p.lora == "per_problem":
                 # more than 256 rows (library GEMMs): one GEMM per LoRA at its own rank (rounded up to a K-block; the rows /
                 # columns beyond the rank are zero) with the bias in the GEMM epilogue.  The batched form multiplies all four
                 # at the widest rank (96/128/128/480 -> 512: 2.4x the flops), runs 4 x [rows, 512, C] at 0.18 PFLOP/s and
                 # expands the bias to [4, rows, C] first: 373 us per layer at 2500 rows against 61 + 56 this way
                 # (profiles/r02_prefill_B25_T100.txt).
-                ups = []
-                hid = None
                 for j in range(p0, 4):
                     kj = lw.lora_k[j]
                     hj = F.linear(mixed[2 + j], lw.lora1[j, :kj])                              # [rows, kj]
                     if j in (1, 3):
                         ops.lora_act_(hj.unsqueeze(0), j)                                      # tanh(w), sigmoid(g)
-                    ups.append(torch.addmm(lw.lbias[j].view(-1), hj, lw.lora2[j, :, :kj].t()))  # + v0 / w0 / a0 / 0
-                up = ups
-              elif not grouped:
+                    up.append(torch.addmm(lw.lbias[j].view(-1), hj, lw.lora2[j, :, :kj].t()))  # + v0 / w0 / a0 / 0
+            else:
                 hid = torch.bmm(mixed[2 + p0:6], lw.lora1[p0:].transpose(1, 2))
-                ops.lora_act_(hid, p0)                                                        # tanh(w), sigmoid(g)
-                if hw and self.skinny_lora_up and hid.shape[2] % 64 == 0:
-                    up = ops.skinny_bmm(hid, lw.lora2[p0:], lw.lbias[p0:], splits=1,             # bias in the epilogue;
-                                        k_of=lw.lora_k[p0:])                                   # padding of the ranks not read
-                else:
-                    up = torch.baddbmm(lw.lbias[p0:], hid, lw.lora2[p0:].transpose(1, 2))     # + v0 / w0 / a0 / 0
-            if grouped or a8:
-                pass
-            elif hw and self.skinny_rkv:
-                rkv = ops.skinny_bmm(mixed[0:3], lw.rkv, splits=2)                             # one launch for R, K, V
-            elif rows >= self.split_rows_min:
-                rkv = new(3, rows, C)                       # three GEMMs at 1.15 PFLOP/s instead of one batched launch at 1.0
-                for j in range(3):
-                    torch.mm(mixed[j], w_rkv[j].t(), out=rkv[j])
-            else:
-                rkv = torch.bmm(mixed[0:3], w_rkv.transpose(1, 2))
-            if side is not None:
-                main.wait_stream(side)
-                for t_ in ([hid] if hid is not None else []) + (list(up) if isinstance(up, list) else [up]):
-                    t_.record_stream(main)
-            r, k, v = rkv[0].view(B, T, C), rkv[1].view(B, T, C), rkv[2].view(B, T, C)
-            vg_pre = up[0].view(B, T, C) if i > 0 else None
-            w, a_pre, g = (up[j - p0].view(B, T, C) for j in (1, 2, 3))
-            if not s1[i].is_contiguous():
-                raise ops._lib.ChirrupAmdError("state[1][layer] view must be contiguous (slice the batch dim only)")
-            if fuse_core:
-                # gating + WKV7 + group-norm/bonus/gate in ONE kernel; k', v', -kk, kk*a, y never reach HBM
-                ops.tmix_wkv7_fused(B, T, C, H, s1[i], r, w, k, v, a_pre, vg_pre, v_first if i > 0 else None, g, lw.k_k,
-                                    lw.k_a, lw.r_k, lw.lnx_w, lw.lnx_b, 64e-5, o_in, elapsed, slot_idx,
-                                    mm8_out=(lw.O8.ry, lw.O8.my, S_o) if a8_out_fused else None)
-                if i == 0:
-                    v_first = v
-            else:
-                ops.tmix_mid(rows, C, k, v, a_pre, vg_pre, v_first if i > 0 else None, lw.k_k, lw.k_a, neg_kk, kka)
-                if i == 0:
-                    v_first = v
-                if self._wkv is ops.forward_seq:
-                    ops.forward_seq(B, T, C, H, s1[i], r, w, k, v, neg_kk, kka, y, elapsed, slot_idx, split_decay=T >= 4)
-                else:
-                    self._wkv(B, T, C, H, s1[i], r, w, k, v, neg_kk, kka, y, elapsed, slot_idx)
-                ops.tmix_post(rows, C, y, r, k, v, g, lw.r_k, lw.lnx_w, lw.lnx_b, 64e-5, o_in)
-            # residual add of the time-mix + LN2 + token shift + one lerp
-            prev = s0[i][1]
-            q8_out = (lw.f_K8.ry, lw.f_K8.my, xs_k, S_k) if q8 else None
-            if a8_out_fused:
-                # o_in holds xs = fp16(o * ry): the uint8 GEMM's core partials, corrected by the LN kernel below (mm8_in)
-                aparts = ops.mm8t_gemm_partial(o_in.view(rows, C), lw.O8.qT, C, gs["att_out"], pbuf_o, tiled=lw.a8_tiled, row_halves=rh["att_out"])
-                ops.add_ln_mix(B, T, C, x, None, x if T == 1 else x_alt, lw.ln2_w, lw.ln2_b, 1e-5, prev,
-                               prev if T == 1 else carry, lw.f_x_k.view(1, C), kin, slot_idx, delta_partials=aparts,
-                               mm8_in=(lw.O8.rx, lw.O8.mx, S_o), mm8_out=q8_out)
-            elif a8:
-                att = ops.mm8t_linear(o_in.view(rows, C), *lw.O8, tiled=lw.a8_tiled).view(B, T, C)
-                ops.add_ln_mix(B, T, C, x, att, x if T == 1 else x_alt, lw.ln2_w, lw.ln2_b, 1e-5, prev,
-                               prev if T == 1 else carry, lw.f_x_k.view(1, C), kin, slot_idx, mm8_out=q8_out)
-            elif hw and self.skinny_att_out and rows >= self.skinny_wide_rows:
-                aparts = ops.skinny_linear_partial(o_in.view(rows, C), lw.O_t if lw.O_t is not None else lw.O, gs["att_out"], pbuf_o, row_halves=rh["att_out"])   # reduce folded into the LN below
-                ops.add_ln_mix(B, T, C, x, None, x if T == 1 else x_alt, lw.ln2_w, lw.ln2_b, 1e-5, prev,
-                               prev if T == 1 else carry, lw.f_x_k.view(1, C), kin, slot_idx, delta_partials=aparts, mm8_out=q8_out)
-            else:
-                att = F.linear(o_in, w_O)
-                ops.add_ln_mix(B, T, C, x, att, x if T == 1 else x_alt, lw.ln2_w, lw.ln2_b, 1e-5, prev,
-                               prev if T == 1 else carry, lw.f_x_k.view(1, C), kin, slot_idx, mm8_out=q8_out)
-            if T > 1:
-                x, x_alt = x_alt, x
-                commit_carry(prev)
-            if q8:
-                if key_fused:
-                    ops.mm8t_gemm_fused(xs_k, lw.f_K8.qT, 4 * C, lw.f_K8.rx, lw.f_K8.mx, S_k, act=1, nxt=(lw.f_V8.ry, lw.f_V8.my, xs_v, S_v),
-                                        tiled=lw.f8_tiled)
-                elif key_pair:
-                    ops.mm8t_gemm_fused(xs_k, lw.f_K8.qT, 4 * C, lw.f_K8.rx, lw.f_K8.mx, S_k, act=1, nxt=(lw.f_V8.ry, lw.f_V8.my, xs_v, S_v),
-                                        tiled=lw.f8_tiled, splits=gs["ffn_key"], partials=pbuf_k)
-                else:
-                    kparts = ops.mm8t_gemm_partial(xs_k, lw.f_K8.qT, 4 * C, gs["ffn_key"], pbuf_k, tiled=lw.f8_tiled, row_halves=rh["ffn_key"])
-                    ops.mm8_reduce_rows(kparts, lw.f_K8.rx, lw.f_K8.mx, S_k, act=1, nxt=(lw.f_V8.ry, lw.f_V8.my, xs_v, S_v))
-                dparts, delta = ops.mm8t_gemm_partial(xs_v, lw.f_V8.qT, C, gs["ffn_value"], pbuf, tiled=lw.f8_tiled, row_halves=rh["ffn_value"]), None
-                dq = (lw.f_V8.rx, lw.f_V8.mx, S_v)
-            elif self.ffn_dtype == torch.int8 and rows > 256 and self.mm8_prefill_dequant:
-                # chunked prefill: above 256 rows a product is MFMA-bound and the ring kernel would re-stream the uint8 tiles once
-                # per 256-row block (2500 rows: 10 x 52 us per product against 290 us for a binary16 library call).  One pass
-                # rebuilds the layer's dequantised matrix as binary16 into a scratch shared by all layers (40-80 us: 67 MB in,
-                # 134 MB out), then the library GEMM of the binary16 path -- what the reference's own mm8_seq_opt does in front of
-                # cuBLAS (rwkv_pip_wrapper.cpp:163-176), with the dequantisation as coded (:76-79) instead of a cast.
-                sK, sV = self._mm8_scratch(4 * C * C)
-                wK16 = ops.mm8_dequant(*lw.f_K8, tiled=lw.f8_tiled, out=sK)          # [4C, C]
-                kf = torch.empty((B, T, 4 * C), dtype=DTYPE, device=dev)
-                self._mm_nt(kin[0].view(rows, C), wK16, kf.view(rows, 4 * C))
-                ops.relu_sq_(kf)
-                wV16 = ops.mm8_dequant(*lw.f_V8, tiled=lw.f8_tiled, out=sV)          # [C, 4C]
-                delta = torch.empty((B, T, C), dtype=DTYPE, device=dev)
-                self._mm_nt(kf.view(rows, 4 * C), wV16, delta.view(rows, C))
-            elif self.ffn_dtype == torch.int8:      # mm8 on the matrix cores, relu^2 fused into the epilogue
-                kf = ops.mm8t_linear(kin[0].view(rows, C), *lw.f_K8, act=1, tiled=lw.f8_tiled)
-                delta = ops.mm8t_linear(kf, *lw.f_V8, tiled=lw.f8_tiled).view(B, T, C)
-            else:
-                if use_parts and self.skinny_ffn_key and rows >= self.skinny_wide_rows:
-                    kf = ops.skinny_linear(kin[0].view(rows, C), lw.f_K_t if lw.f_K_t is not None else lw.f_K, act=1, splits=gs["ffn_key"],
-                                           row_halves=rh["ffn_key"])
-                else:
-                    # the library's choice for (rows x C) . (4C x C)^T runs at 0.83 PFLOP/s at 2500 rows, the same product as two row
-                    # halves at 1.16 (404 vs 290 us) -- but at 1024-2200 rows the single call is the faster one: measured per shape
-                    kf = torch.empty((B, T, 4 * C), dtype=DTYPE, device=dev)
-                    self._mm_nt(kin[0].view(rows, C), w_fK, kf.view(rows, 4 * C))
-                    ops.relu_sq_(kf)
-                if rows == 1 and lw.f_V_rows is not None:
-                    delta = ops.rwkv_mm_sparsity(kf.view(-1), lw.f_V_rows).view(1, 1, C)
-                elif use_parts:
-                    # K = 4C >> N = C at decode batch sizes: the hand-written LDS-DMA ring GEMM streams this
-                    # matrix 1.35x faster than the library (53.8 vs 73.6 us at 7.2B / bsz 200, DESIGN.md section 5);
-                    # its split-K partials are summed in the prologue of the NEXT add_ln_mix (no reduce launch)
-                    dparts, delta = ops.skinny_linear_partial(kf.view(rows, 4 * C), lw.f_V_t if lw.f_V_t is not None else lw.f_V.t(), gs["ffn_value"], pbuf, row_halves=rh["ffn_value"]), None
-                elif rows >= self.tune_mm_min_rows and w_fV.t().is_contiguous():
-                    delta = torch.empty((B, T, C), dtype=DTYPE, device=dev)
-                    self._mm_nt(kf.view(rows, 4 * C), w_fV.t(), delta.view(rows, C))     # (ffn.value keeps its [C, 4C] bytes: NT form)
-                else:
-                    delta = kf @ w_fV
-        if dparts is not None and (T > 1 and not full_output):
-            delta, dparts = dparts.sum(0).to(DTYPE).view(B, T, C), None      # e.g. B=2, T=100: only the last rows are needed
-        if T > 1 and not full_output:
-            x, delta, rows_out = x[:, -1, :].contiguous(), delta[:, -1, :].contiguous(), (B, 1)
+                ops.lora_act_(hid, p0)                                                            # tanh(w), sigmoid(g)
+                # bmm_ring: bias in the epilogue, the padding of the ranks not read; bmm_baddbmm: + v0 / w0 / a0 / 0
+                up = (ops.skinny_bmm(hid, lw.lora2[p0:], lw.lbias[p0:], splits=1, k_of=lw.lora_k[p0:]) if p.lora == "bmm_ring" else
+                      torch.baddbmm(lw.lbias[p0:], hid, lw.lora2[p0:].transpose(1, 2)))
+        if p.rkv == "skinny_bmm":
+            rkv = ops.skinny_bmm(mixed[0:3], lw.rkv, splits=2)                             # one launch for R, K, V
+        elif p.rkv == "mm3":
+            rkv = new(3, rows, C)                       # three GEMMs at 1.15 PFLOP/s instead of one batched launch at 1.0
+            for j in range(3):
+                torch.mm(mixed[j], w_rkv[j].t(), out=rkv[j])
+        elif p.rkv == "bmm":
+            rkv = torch.bmm(mixed[0:3], w_rkv.transpose(1, 2))
+        main.wait_stream(side)
+        for t_ in ([hid] if hid is not None else []) + (up if isinstance(up, list) else [up]):
+            t_.record_stream(main)
+        return rkv, up
+
+    def _tmix_core(self, p: _Plan, f, i, lw: _Layer, rkv, up, S):
+        """k/kk/a/v gating + WKV7 state update of S + group norm / bonus / gate into o_in."""
+        B, T, C, H = f.B, f.T, f.C, self.n_head
+        r, k, v = (rkv[j].view(B, T, C) for j in range(3))
+        vg_pre, w, a_pre, g = ([None] if i == 0 else []) + [u.view(B, T, C) for u in up]     # (layer 0 has no v gate)
+        v_first, f.v_first = (f.v_first, f.v_first) if i > 0 else (None, v)      # layer 0's v is every later layer's v_first
+        if p.fuse_core:
+            # gating + WKV7 + group-norm/bonus/gate in ONE kernel; k', v', -kk, kk*a, y never reach HBM
+            ops.tmix_wkv7_fused(B, T, C, H, S, r, w, k, v, a_pre, vg_pre, v_first, g, lw.k_k, lw.k_a, lw.r_k, lw.lnx_w,
+                                lw.lnx_b, 64e-5, f.o_in, f.elapsed, f.slot_idx,
+                                mm8_out=(lw.O8.ry, lw.O8.my, f.S_o) if p.att_out == "mm8_fused" else None)
+            return
+        ops.tmix_mid(f.rows, C, k, v, a_pre, vg_pre, v_first, lw.k_k, lw.k_a, f.neg_kk, f.kka)
+        kw = {"split_decay": T >= 4} if self._wkv is ops.forward_seq else {}      # (a wkv_impl test hook takes no split_decay)
+        self._wkv(B, T, C, H, S, r, w, k, v, f.neg_kk, f.kka, f.y, f.elapsed, f.slot_idx, **kw)
+        ops.tmix_post(f.rows, C, f.y, r, k, v, g, lw.r_k, lw.lnx_w, lw.lnx_b, 64e-5, f.o_in)
+
+    def _att_output(self, p: _Plan, f, lw: _Layer, prev, w_O):
+        """att.output of o_in, then the residual add of the time-mix + LN2 + token shift + one lerp into kin."""
+        rows, C, gs, rh = f.rows, f.C, self.gemm_splits, p.row_halves
+        att = parts = mm8_in = None
+        o2 = f.o_in.view(rows, C)
+        if p.att_out == "mm8_fused":
+            # o_in holds xs = fp16(o * ry): the uint8 GEMM's core partials, corrected by the LN kernel below (mm8_in)
+            parts = ops.mm8t_gemm_partial(o2, lw.O8.qT, C, gs["att_out"], f.pbuf_o, tiled=lw.a8_tiled, row_halves=rh["att_out"])
+            mm8_in = (lw.O8.rx, lw.O8.mx, f.S_o)
+        elif p.att_out == "mm8":
+            att = ops.mm8t_linear(o2, *lw.O8, tiled=lw.a8_tiled).view(f.B, f.T, C)
+        elif p.att_out == "ring":                   # its reduce folded into LN2
+            parts = ops.skinny_linear_partial(o2, lw.ring("O"), gs["att_out"], f.pbuf_o, row_halves=rh["att_out"])
         else:
-            rows_out = (B, T)
-        xo = new(rows_out[0], rows_out[1], C)
-        ops.add_ln_mix(rows_out[0], rows_out[1], C, x, delta, None, z["ln_out.weight"], z["ln_out.bias"], 1e-5, None, None,
-                       None, xo, delta_partials=dparts, mm8_in=dq)
+            att = F.linear(f.o_in, w_O)
+        q8_out = (lw.f_K8.ry, lw.f_K8.my, f.xs_k, f.S_k) if p.ffn_value == "mm8_parts" else None
+        self._add_ln(f, lw.ln2_w, lw.ln2_b, prev, lw.f_x_k.view(1, C), f.kin, att, parts, mm8_in, q8_out)
+
+    def _channel_mix(self, p: _Plan, f, lw: _Layer, w_fK, w_fV):
+        """ffn.key (+ relu^2) and ffn.value of kin: leaves f.delta, or the split-K partials f.dparts (with the mm8 corrections
+        f.dq) that the next LN kernel sums."""
+        B, T, C, rows, gs, rh = f.B, f.T, f.C, f.rows, self.gemm_splits, p.row_halves
+        kin = f.kin[0].view(rows, C)
+        if p.ffn_value == "mm8_parts":
+            K8, V8, nxt = lw.f_K8, lw.f_V8, (lw.f_V8.ry, lw.f_V8.my, f.xs_v, f.S_v)
+            if p.ffn_key == "mm8_partial":
+                kparts = ops.mm8t_gemm_partial(f.xs_k, K8.qT, 4 * C, gs["ffn_key"], f.pbuf_k, tiled=lw.f8_tiled, row_halves=rh["ffn_key"])
+                ops.mm8_reduce_rows(kparts, K8.rx, K8.mx, f.S_k, act=1, nxt=nxt)
+            else:                                   # (mm8_pair: split over K, reduced inside the launch into pbuf_k)
+                ops.mm8t_gemm_fused(f.xs_k, K8.qT, 4 * C, K8.rx, K8.mx, f.S_k, act=1, nxt=nxt, tiled=lw.f8_tiled,
+                                    splits=gs["ffn_key"] if p.ffn_key == "mm8_pair" else None, partials=f.pbuf_k)
+            f.dparts = ops.mm8t_gemm_partial(f.xs_v, V8.qT, C, gs["ffn_value"], f.pbuf, tiled=lw.f8_tiled, row_halves=rh["ffn_value"])
+            f.delta, f.dq = None, (V8.rx, V8.mx, f.S_v)
+        elif p.ffn_value == "mm8_dequant":
+            # chunked prefill: above 256 rows a product is MFMA-bound and the ring kernel would re-stream the uint8 tiles once
+            # per 256-row block (2500 rows: 10 x 52 us per product against 290 us for a binary16 library call).  One pass
+            # rebuilds the layer's dequantised matrix as binary16 into a scratch shared by all layers (40-80 us: 67 MB in,
+            # 134 MB out), then the library GEMM of the binary16 path -- what the reference's own mm8_seq_opt does in front of
+            # cuBLAS (rwkv_pip_wrapper.cpp:163-176), with the dequantisation as coded (:76-79) instead of a cast.
+            sK, sV = self._mm8_scratch(4 * C * C)
+            wK16 = ops.mm8_dequant(*lw.f_K8, tiled=lw.f8_tiled, out=sK)          # [4C, C]
+            kf = f.new(B, T, 4 * C)
+            self._mm_nt(kin, wK16, kf.view(rows, 4 * C))
+            ops.relu_sq_(kf)
+            wV16 = ops.mm8_dequant(*lw.f_V8, tiled=lw.f8_tiled, out=sV)          # [C, 4C]
+            f.delta = f.new(B, T, C)
+            self._mm_nt(kf.view(rows, 4 * C), wV16, f.delta.view(rows, C))
+        elif p.ffn_value == "mm8":                  # mm8 on the matrix cores, relu^2 fused into the epilogue
+            kf = ops.mm8t_linear(kin, *lw.f_K8, act=1, tiled=lw.f8_tiled)
+            f.delta = ops.mm8t_linear(kf, *lw.f_V8, tiled=lw.f8_tiled).view(B, T, C)
+        else:
+            if p.ffn_key == "ring":
+                kf = ops.skinny_linear(kin, lw.ring("f_K"), act=1, splits=gs["ffn_key"], row_halves=rh["ffn_key"])
+            else:
+                # the library's choice for (rows x C) . (4C x C)^T runs at 0.83 PFLOP/s at 2500 rows, the same product as two row
+                # halves at 1.16 (404 vs 290 us) -- but at 1024-2200 rows the single call is the faster one: measured per shape
+                kf = f.new(B, T, 4 * C)
+                self._mm_nt(kin, w_fK, kf.view(rows, 4 * C))
+                ops.relu_sq_(kf)
+            if p.ffn_value == "sparse":
+                f.delta = ops.rwkv_mm_sparsity(kf.view(-1), lw.f_V_rows).view(1, 1, C)
+            elif p.ffn_value == "ring":
+                # K = 4C >> N = C at decode batch sizes: the hand-written LDS-DMA ring GEMM streams this
+                # matrix 1.35x faster than the library (53.8 vs 73.6 us at 7.2B / bsz 200, DESIGN.md section 5);
+                # its split-K partials are summed in the prologue of the NEXT add_ln_mix (no reduce launch)
+                f.dparts = ops.skinny_linear_partial(kf.view(rows, 4 * C), lw.ring("f_V"), gs["ffn_value"], f.pbuf, row_halves=rh["ffn_value"])
+            elif p.ffn_value == "mm_nt":
+                f.delta = f.new(B, T, C)
+                self._mm_nt(kf.view(rows, 4 * C), w_fV.t(), f.delta.view(rows, C))     # (ffn.value keeps its [C, 4C] bytes: NT form)
+            else:
+                f.delta = kf @ w_fV
+
+    def _ln_out_head(self, p: _Plan, f, full_output, s2):
+        """Residual add of the last channel-mix + ln_out (last token of each sequence unless full_output) + head."""
+        z, B, T, C, T_out = self.z, f.B, f.T, f.C, f.T
+        x, delta, dparts = f.x, f.delta, f.dparts
+        if T > 1 and not full_output:
+            if dparts is not None:
+                delta, dparts = dparts.sum(0).to(DTYPE).view(B, T, C), None      # e.g. B=2, T=100: only the last rows are needed
+            x, delta, T_out = x[:, -1, :].contiguous(), delta[:, -1, :].contiguous(), 1
+        xo = f.new(B, T_out, C)
+        ops.add_ln_mix(B, T_out, C, x, delta, None, z["ln_out.weight"], z["ln_out.bias"], 1e-5, None, None,
+                       None, xo, delta_partials=dparts, mm8_in=f.dq)
         if not full_output:
             xo = xo.view(B, C)
-        if slot_idx is not None:
-            ops.advance_elapsed(s2, T, slot_idx)              # state[2] += T over the slot list, one launch
-        if self.head8 is not None:
+        if f.slot_idx is not None:
+            ops.advance_elapsed(s2, T, f.slot_idx)              # state[2] += T over the slot list, one launch
+        if p.head == "mm8":
             return ops.mm8t_linear(xo.reshape(-1, C), *self.head8, tiled=self._head8_tiled).view(*xo.shape[:-1], -1)
-        if (hw or not self.keep_row_major) and self.skinny_head and xo.shape[0] <= 256:
+        if p.head == "ring":
             if self._head_t is None:
                 hwt = z["head.weight"]
                 self._head_t = ops.tile_weight(hwt) if (self.tiled_weights and hwt.shape[0] % 128 == 0 and hwt.shape[1] % 64 == 0) else hwt
             return ops.skinny_linear(xo, self._head_t, splits=1)
-        return F.linear(xo, self._head_row_major())
+        return F.linear(xo, z["head.weight"])          # (a tile-image-only model rebuilds it: _LazyWeights)
 
     def _tmix(self, layer_id, lw: _Layer, x, x_prev, v_first, S, elapsed_t):
         """Time-mix block, arithmetic of RWKV_x070_TMix_seq_batch (rwkv7.py:618-649).
