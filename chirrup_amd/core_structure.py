@@ -6,6 +6,9 @@ FinishReason :40-55, defaults :13-36) because the worker protocol and the OpenAI
 written against them.  No arithmetic lives here.
 """
 import enum
+import math
+import numbers
+import operator
 import queue
 import uuid
 from dataclasses import dataclass, field
@@ -24,6 +27,7 @@ DEFAULT_SAMPLING_CONFIG: Dict[str, Any] = {
     "penalty_decay": 0.996,
     "max_tokens": 8192,
 }
+LOGIT_BIAS_MAX = 1024          # entries of one request's logit_bias (the worker's per-slot list capacity)
 
 
 class FinishReason(enum.IntEnum):
@@ -91,6 +95,12 @@ class Task:
     # ("token_generated", ...) payload; a forbidden token can therefore appear among the top_logprobs
     logprobs: bool = False
     top_logprobs: int = 0
+    # sampled rows draw from Philox4x32-10 keyed by this seed (an int64 is read as its two's complement uint64), one counter per
+    # sampled token: the ids then depend on (seed, draw index) and the logits only, not on the slot or the other requests
+    seed: Optional[int] = None
+    # {token id: bias}: added to the raw logits (binary32, one rounding to binary16, clamped to +-65504) after the forbidden
+    # tokens and before the penalties; it moves greedy rows too, and logprobs still measure the raw output
+    logit_bias: Dict[int, float] = field(default_factory=dict)
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -102,9 +112,34 @@ class Task:
             self.task_id = str(uuid.uuid4())
         if not 0 <= self.top_logprobs <= 20 or (self.top_logprobs > 0 and not self.logprobs):
             raise ValueError("top_logprobs must be in 0..20, and a value > 0 requires logprobs")
+        if self.seed is not None:
+            self.seed = _integer(self.seed, "seed")
+            if not -(1 << 63) <= self.seed < (1 << 64):
+                raise ValueError("seed must be an integer in [-2^63, 2^64)")
+        bias = dict(self.logit_bias or {})
+        if len(bias) > LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias holds {len(bias)} entries, at most {LOGIT_BIAS_MAX} are allowed")
+        checked = {}
+        for t, v in bias.items():
+            t = _integer(t, "logit_bias token id")
+            if t < 0 or t in checked:
+                raise ValueError(f"logit_bias: token id {t} is negative or repeated")
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+                raise ValueError(f"logit_bias: the bias of token {t} is not a finite number")
+            checked[t] = float(v)
+        self.logit_bias = checked
 
     def is_finished(self) -> bool:
         return RequestStatus.is_finished(self.request_status)
+
+
+def _integer(x, what: str) -> int:
+    if isinstance(x, bool):
+        raise ValueError(f"{what} must be an integer, got {x!r}")
+    try:
+        return operator.index(x)
+    except TypeError:
+        raise ValueError(f"{what} must be an integer, got {x!r}") from None
 
 
 @dataclass

@@ -806,3 +806,93 @@ extern "C" int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits
                        static_cast<const f16 *>(logits), rows, target_ids, target_rows, out_lp, out_ids);
     return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Per-request seeded draws: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011) with the
+// standard multipliers and Weyl key increments.  A seeded request's uniform for its i-th sampled token is a pure function of
+// (seed, i): key = (lo32(seed), hi32(seed)), counter = (i, 0, 0, 0), u = (x0 >> 8) * 2^-24 -- exact in binary32, in
+// [0, 1 - 2^-24].  The counter lives in a per-slot table that the draw advances, so the draw does not depend on the slot, the
+// batch, the step or on graph / eager mode.
+namespace {
+
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
+__device__ __forceinline__ uint32_t philox_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; round++) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0, p1 = (uint64_t)kPhiloxM1 * c2;      // 32 x 32 -> 64
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+        k0 += kPhiloxW0, k1 += kPhiloxW1;
+    }
+    return c0;
+}
+
+__global__ __launch_bounds__(256) void seeded_uniform_kernel(const int n, const int32_t *__restrict__ rows,
+                                                             const int32_t *__restrict__ slot_idx, const uint64_t *__restrict__ seeds,
+                                                             const int32_t *__restrict__ seeded, uint32_t *__restrict__ counters,
+                                                             float *__restrict__ uniform) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = rows[i];
+    const int s = slot_idx[r];
+    if (!seeded[s]) return;                                  // unseeded rows keep the caller's uniform
+    const uint64_t seed = seeds[s];
+    const uint32_t ctr = counters[s];
+    const uint32_t x0 = philox_x0(ctr, 0u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    uniform[i] = (float)(x0 >> 8) * 0x1p-24f;
+    counters[s] = ctr + 1u;
+}
+
+// Logit bias: logits[row][id] = fp16(clamp(float(l) + bias, -65504, 65504)) for each entry (id, bias) of the row's slot list, ids
+// outside [0, V) skipped; non-finite logits (a forbidden -inf) are left as they are.  One workgroup per row, lanes over the
+// entries; the ids of one list are distinct (the worker builds them from a dict), so no two lanes touch the same logit.
+constexpr int kBiasThreads = 256;
+
+__global__ __launch_bounds__(kBiasThreads) void apply_logit_bias_kernel(const int V, const int cap, f16 *__restrict__ logits,
+                                                                        const int32_t *__restrict__ slot_idx,
+                                                                        const int32_t *__restrict__ counts,
+                                                                        const int32_t *__restrict__ ids,
+                                                                        const float *__restrict__ values) {
+    const int row = blockIdx.x;
+    const int64_t s = slot_idx ? (int64_t)slot_idx[row] : (int64_t)row;
+    int cnt = counts[s];
+    cnt = cnt < cap ? cnt : cap;
+    f16 *lg = logits + (int64_t)row * V;
+    const int32_t *id_s = ids + s * cap;
+    const float *val_s = values + s * cap;
+    for (int j = threadIdx.x; j < cnt; j += kBiasThreads) {
+        const int id = id_s[j];
+        if (id < 0 || id >= V) continue;
+        const float l = (float)lg[id];
+        if (!__builtin_isfinite(l)) continue;
+        const float b = l + val_s[j];
+        lg[id] = (f16)fminf(fmaxf(b, -65504.f), 65504.f);
+    }
+}
+
+}  // namespace
+
+extern "C" int rwkv7_seeded_uniform(int n_rows, const int32_t *rows, const int32_t *slot_idx, const uint64_t *seeds,
+                                    const int32_t *seeded, uint32_t *counters, float *uniform, void *stream) {
+    if (n_rows < 0) return CHIRRUP_E_SHAPE;
+    if (n_rows == 0) return 0;
+    if (!rows || !slot_idx || !seeds || !seeded || !counters || !uniform) return CHIRRUP_E_NULL;
+    if (reinterpret_cast<uintptr_t>(seeds) & 7) return CHIRRUP_E_ALIGN;
+    hipLaunchKernelGGL(seeded_uniform_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       n_rows, rows, slot_idx, seeds, seeded, counters, uniform);
+    return (int)hipGetLastError();
+}
+
+extern "C" int rwkv7_apply_logit_bias(int n_rows, int V, int cap, void *logits, const int32_t *slot_idx, const int32_t *counts,
+                                      const int32_t *ids, const float *values, void *stream) {
+    if (n_rows < 0 || V <= 0 || cap <= 0) return CHIRRUP_E_SHAPE;
+    if (n_rows == 0) return 0;
+    if (!logits || !counts || !ids || !values) return CHIRRUP_E_NULL;
+    if (reinterpret_cast<uintptr_t>(logits) & 1) return CHIRRUP_E_ALIGN;
+    hipLaunchKernelGGL(apply_logit_bias_kernel, dim3((unsigned)n_rows), dim3(kBiasThreads), 0, static_cast<hipStream_t>(stream), V, cap,
+                       static_cast<f16 *>(logits), slot_idx, counts, ids, values);
+    return (int)hipGetLastError();
+}

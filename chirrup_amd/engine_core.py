@@ -84,6 +84,7 @@ class AsyncEngineCore:
         self.event_loop: Optional[asyncio.AbstractEventLoop] = None
         self.is_initialized = False
         self.is_shutdown = False
+        self.vocab_size = None                        # model_config.vocab_size, set by init(): completion() checks logit_bias ids
         self.tokenizer = tokenizer
         self._worker_factory = worker_factory
 
@@ -165,6 +166,7 @@ class AsyncEngineCore:
             self.event_loop = asyncio.new_event_loop()
             asyncio.set_event_loop(self.event_loop)
         self.worker_event_queue = ThreadSafeAsyncQueue(self.event_loop, asyncio.Queue(maxsize=worker_num * 100))
+        self.vocab_size = int(model_config.vocab_size)
         self.is_initialized = True
         if self.tokenizer is None:
             from .tokenizer import TRIE_TOKENIZER
@@ -214,12 +216,16 @@ class AsyncEngineCore:
                    stop_tokens: Optional[List[int]] = DEFAULT_STOP_TOKENS, forbidden_tokens: Optional[List[int]] = None,
                    max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], task_id: Optional[str] = None,
                    cache_prefill: bool = False, cache_prefill_padding: int = 0,
-                   return_logits: bool = False, logprobs: bool = False, top_logprobs: int = 0) -> AsyncEngineCompletion:
+                   return_logits: bool = False, logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
+                   logit_bias: Optional[Dict[int, float]] = None) -> AsyncEngineCompletion:
         assert not (state is not None and prefill_tokens is None), "prefill_tokens cannot be None when state is not None"
         if not self.is_initialized:
             raise RuntimeError("Engine not initialized")
         if self.is_shutdown:
             raise RuntimeError("Engine has been shutdown")
+        bad = [t for t in (logit_bias or {}) if isinstance(t, int) and self.vocab_size is not None and t >= self.vocab_size]
+        if bad:
+            raise ValueError(f"logit_bias: token id {bad[0]} is outside the vocabulary (size {self.vocab_size})")
         if not prefill_tokens:
             prefill_tokens = self.tokenizer.encode(prompt_str)
         task_id = task_id or str(uuid.uuid4())
@@ -235,7 +241,8 @@ class AsyncEngineCore:
                                      frequency_penalty=frequency_penalty, penalty_decay=penalty_decay,
                                      stop_tokens=stop_tokens, forbidden_tokens=forbidden_tokens, max_tokens=max_tokens,
                                      cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
-                                     return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs)
+                                     return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
+                                     logit_bias=logit_bias)
 
     def _on_worker_fatal(self, worker, exc) -> None:
         """Called on a dying worker's thread.  When it was the last live worker, nobody will ever pick up the

@@ -5,7 +5,7 @@ Same surface as the reference's chirrup/interface.py:31-142: an async iterator o
 submitting its Task on first iteration, with ``get_full_completion()`` and ``abort()``."""
 import asyncio
 import queue
-from typing import Any, List, Optional
+from typing import Any, Dict, List, Optional
 
 from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, Task
 
@@ -20,7 +20,8 @@ class AsyncEngineCompletion:
                  stop_tokens: Optional[List[int]] = DEFAULT_STOP_TOKENS, forbidden_tokens: Optional[List[int]] = None,
                  max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], cache_prefill: bool = False,
                  cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None,
-                 logprobs: bool = False, top_logprobs: int = 0):
+                 logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
+                 logit_bias: Optional[Dict[int, float]] = None):
         self.task_id = task_id
         # the worker polls it for ("abort", None); a process-mode engine passes a channel that reaches the worker's process
         self.task_event_queue = task_event_queue if task_event_queue is not None else queue.Queue()
@@ -31,7 +32,8 @@ class AsyncEngineCompletion:
                          frequency_penalty=frequency_penalty, penalty_decay=penalty_decay, max_tokens=max_tokens,
                          stop_tokens=stop_tokens, forbidden_tokens=list(forbidden_tokens or []),
                          cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
-                         return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs)
+                         return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
+                         logit_bias=dict(logit_bias or {}))
         self._task_queue = task_queue
         self._submitted = False
         self.is_finished = False

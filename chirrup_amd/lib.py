@@ -60,6 +60,8 @@ SIGNATURES = {
     "rwkv7_penalize_argmax_listed": (_i, [_i, _i] + [_vp] * 9 + [_i, _vp]),
     "rwkv7_sample_topp": (_i, [_i, _i] + [_vp] * 9),
     "rwkv7_token_logprobs": (_i, [_i, _i, _i] + [_vp] * 7),
+    "rwkv7_seeded_uniform": (_i, [_i] + [_vp] * 7),
+    "rwkv7_apply_logit_bias": (_i, [_i, _i, _i] + [_vp] * 6),
     "rwkv7_embed_rows": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _vp]),
     "rwkv7_advance_elapsed": (_i, [_i, _i, _vp, _vp, _vp]),
     "rwkv7_copy_slot_rows": (_i, [_i, _i, _vp, _vp, _vp, _vp]),

@@ -1155,6 +1155,131 @@ def _token_logprobs_torch(logits, k, targets, rows, target_rows):
     return lp, order.to(torch.int32)
 
 
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 of counters uint32 [..., 4] and keys uint32 [..., 2] (numpy, broadcast): the host form of the draw in
+    rwkv7_seeded_uniform and the reference the GPU tests compare against.  Returns uint32 [..., 4]."""
+    import numpy as np
+
+    c = [np.asarray(ctr, np.uint64)[..., j] & 0xFFFFFFFF for j in range(4)]
+    k0, k1 = (np.asarray(key, np.uint64)[..., j] & 0xFFFFFFFF for j in range(2))
+    m0, m1 = np.uint64(PHILOX_M[0]), np.uint64(PHILOX_M[1])
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]                                  # 32 x 32 -> 64, exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & mask]
+        k0, k1 = (k0 + np.uint64(PHILOX_W[0])) & mask, (k1 + np.uint64(PHILOX_W[1])) & mask
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def seed_bits(seed: int) -> int:
+    """The seed as the uint64 the generator keys on: an int64 (a negative seed) is reinterpreted as two's complement."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise ValueError(f"seed {seed} is outside [-2^63, 2^64)")
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def seed_int64(seed: int) -> int:
+    """seed_bits as the int64 of the same bits (the worker's seed table is an int64 tensor)."""
+    b = seed_bits(seed)
+    return b - (1 << 64) if b >> 63 else b
+
+
+def philox_uniform(seed: int, i):
+    """The uniform of a seeded request's draw(s) i (int or array): (x0 >> 8) * 2^-24 of Philox(counter (i, 0, 0, 0),
+    key (lo32(seed), hi32(seed))), as binary32."""
+    import numpy as np
+
+    s = seed_bits(seed)
+    i = np.asarray(i, np.uint64)
+    ctr = np.stack([i, np.zeros_like(i), np.zeros_like(i), np.zeros_like(i)], axis=-1)
+    x0 = philox4x32_10(ctr, np.array([s & 0xFFFFFFFF, s >> 32], np.uint64))[..., 0]
+    return ((x0 >> np.uint32(8)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
+
+
+def seeded_uniform(rows, slot_idx, seeds, seeded, counters, uniform) -> None:
+    """Overwrites the uniforms of the seeded rows with their Philox draws (include/chirrup_amd.h: rwkv7_seeded_uniform): for row
+    list entry i, slot s = slot_idx[rows[i]]; when seeded[s], uniform[i] = philox_uniform(seeds[s], counters[s]) and counters[s]
+    += 1.  rows int32 [n]; slot_idx int32; seeds int64 (the uint64 bits), seeded int32, counters int32 (uint32 bits) per slot;
+    uniform fp32 [n].  CPU tensors take the numpy form (fake backends); GPU tensors always take the kernel."""
+    n = rows.numel()
+    if uniform.dtype != torch.float32 or uniform.numel() != n:
+        raise _lib.ChirrupAmdError(f"uniform: expected fp32 with {n} elements")
+    if not rows.is_cuda:
+        _seeded_uniform_host(rows, slot_idx, seeds, seeded, counters, uniform)
+        return
+    _chk(rows, "rows", torch.int32, (n,))
+    _chk(slot_idx, "slot_idx", torch.int32)
+    _chk(seeds, "seeds", torch.int64)
+    _chk(seeded, "seeded", torch.int32, tuple(seeds.shape))
+    _chk(counters, "counters", torch.int32, tuple(seeds.shape))
+    _chk(uniform, "uniform", torch.float32, (n,))
+    if n == 0:
+        return
+    rc = _lib.load().rwkv7_seeded_uniform(n, _ptr(rows), _ptr(slot_idx), _ptr(seeds), _ptr(seeded), _ptr(counters), _ptr(uniform),
+                                          _stream())
+    _lib.check(rc, "rwkv7_seeded_uniform")
+
+
+def _seeded_uniform_host(rows, slot_idx, seeds, seeded, counters, uniform):
+    sl = slot_idx.tolist()
+    for i, r in enumerate(rows.tolist()):
+        s = sl[r]
+        if int(seeded[s]):
+            c = int(counters[s]) & 0xFFFFFFFF
+            uniform[i] = float(philox_uniform(int(seeds[s]), c))
+            counters[s] = (c + 1) - (1 << 32) if c + 1 >= (1 << 31) else c + 1     # uint32 bits in an int32 table
+
+
+def apply_logit_bias(logits, slot_idx, counts, ids, values) -> None:
+    """Adds each row's slot list of biases to fp16 logits [n, V] in place (include/chirrup_amd.h: rwkv7_apply_logit_bias):
+    logits[i, id] = fp16(clamp(float(l) + value, -65504, 65504)) for the first counts[s] entries (id, value) of ids / values
+    [S, cap] at s = slot_idx[i] (i without slot_idx), ids outside [0, V) skipped, non-finite logits unchanged.  CPU tensors take
+    the numpy form (fake backends); GPU tensors always take the kernel."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or not logits.is_contiguous():
+        raise _lib.ChirrupAmdError("logits: expected contiguous fp16 [n,V]")
+    n, V = logits.shape
+    if ids.dim() != 2 or tuple(values.shape) != tuple(ids.shape) or counts.numel() != ids.shape[0]:
+        raise _lib.ChirrupAmdError("ids / values: expected [S, cap] each, counts [S]")
+    cap = ids.shape[1]
+    if not logits.is_cuda:
+        _apply_logit_bias_host(logits, slot_idx, counts, ids, values)
+        return
+    if slot_idx is not None:
+        _chk(slot_idx, "slot_idx", torch.int32, (n,))
+    _chk(counts, "counts", torch.int32)
+    _chk(ids, "ids", torch.int32)
+    _chk(values, "values", torch.float32)
+    if n == 0:
+        return
+    rc = _lib.load().rwkv7_apply_logit_bias(n, V, cap, _ptr(logits), _ptr(slot_idx), _ptr(counts), _ptr(ids), _ptr(values), _stream())
+    _lib.check(rc, "rwkv7_apply_logit_bias")
+
+
+def _apply_logit_bias_host(logits, slot_idx, counts, ids, values):
+    import numpy as np
+
+    n, V = logits.shape
+    cap = ids.shape[1]
+    slots = slot_idx.tolist() if slot_idx is not None else list(range(n))
+    for i, s in enumerate(slots):
+        c = min(int(counts[s]), cap)
+        if c <= 0:
+            continue
+        t = ids[s, :c].numpy().astype(np.int64)
+        b = values[s, :c].numpy().astype(np.float32)
+        ok = (t >= 0) & (t < V)
+        t, b = t[ok], b[ok]
+        row = logits[i].numpy()                                # a view: the update is in place
+        lv = row[t].astype(np.float32)
+        fin = np.isfinite(lv)
+        row[t[fin]] = np.clip(lv[fin] + b[fin], np.float32(-65504), np.float32(65504)).astype(np.float16)
+
+
 def lora_act_(hbuf, first_plane: int) -> None:
     """hbuf [n, rows, D] fp16, planes first_plane.. of [v, w, a, g]: tanh on w, sigmoid on g."""
     _chk16("hbuf", hbuf)

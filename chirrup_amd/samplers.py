@@ -22,6 +22,12 @@ import torch.nn.functional as F
 def sample_logits_rwkv_pip_compatible(logits: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
                                       top_k: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """logits [B,V]; temperature, top_p [B,1] float; top_k [B,1] int.  Returns int64 ids [B]."""
+    probs = kept_weights(logits, temperature, top_p, top_k)
+    return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(-1)
+
+
+def kept_weights(logits: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor, top_k: torch.Tensor) -> torch.Tensor:
+    """The un-normalised weights sample_logits_rwkv_pip_compatible draws from: softmax, top-p and top-k filters, ** (1/T)."""
     B, V = logits.shape
     greedy = temperature == 0
     temperature = torch.where(greedy, torch.ones_like(temperature), temperature)
@@ -44,7 +50,21 @@ def sample_logits_rwkv_pip_compatible(logits: torch.Tensor, temperature: torch.T
     hot = temperature != 1.0
     if bool(hot.any()):
         probs = torch.where(hot.expand_as(probs), probs ** (1.0 / temperature.float()), probs)
-    return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(-1)
+    return probs
+
+
+def sample_inverse_cdf(logits: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor, top_k: torch.Tensor,
+                       uniform: torch.Tensor) -> torch.Tensor:
+    """The draw of the seeded rows off the HIP sampler: the kept weights of sample_logits_rwkv_pip_compatible, then the
+    sample_topp kernel's rule -- an inverse-CDF walk in token order, float64 here: the first token of positive weight whose
+    running sum exceeds uniform * total; the last token of positive weight when none does.  uniform fp32 [B].  Returns int64 [B]."""
+    w = kept_weights(logits, temperature, top_p, top_k).double()
+    cum = torch.cumsum(w, dim=-1)
+    want = (uniform.double() * cum[:, -1]).unsqueeze(1)
+    pick = torch.searchsorted(cum, want, right=True).squeeze(1)
+    V = w.shape[1]
+    last = V - 1 - torch.argmax(torch.flip(w > 0, dims=[1]).to(torch.uint8), dim=1)
+    return torch.where(pick < V, pick, last)
 
 
 def is_greedy_row(temperature: float, top_p: float, top_k: int) -> bool:

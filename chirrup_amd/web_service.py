@@ -19,7 +19,7 @@ from fastapi import FastAPI, HTTPException
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, model_validator
 
-from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS
+from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, LOGIT_BIAS_MAX
 from .state_cache import SimpleStateCache
 
 KEEP_ALIVE_S = 10.0
@@ -50,12 +50,34 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     # tokens) and of the top_logprobs most likely ids at each position (OpenAI's choices[0].logprobs.content)
     logprobs: bool = False
     top_logprobs: Optional[int] = Field(None, ge=0, le=20)
+    # OpenAI's seed: sampled tokens draw from a generator keyed by it (reproducible for the same logits); logit_bias: token id
+    # (a decimal string) -> a bias in [-100, 100] added to that token's logit
+    seed: Optional[int] = Field(None, ge=-(1 << 63), lt=1 << 64)
+    logit_bias: Optional[Dict[str, float]] = None
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):
         if self.top_logprobs is not None and not self.logprobs:
             raise ValueError("top_logprobs requires logprobs")
         return self
+
+    @model_validator(mode="after")
+    def _logit_bias_entries(self):
+        seen = set()
+        for key, value in (self.logit_bias or {}).items():
+            if not re.fullmatch(r"[0-9]+", key):
+                raise ValueError(f"logit_bias: key {key!r} is not a token id")
+            if int(key) in seen:
+                raise ValueError(f"logit_bias: token id {int(key)} appears twice")
+            seen.add(int(key))
+            if not -100.0 <= value <= 100.0:
+                raise ValueError(f"logit_bias: the bias of token {key} is outside [-100, 100]")
+        if len(seen) > LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries")
+        return self
+
+    def token_bias(self) -> Dict[int, float]:
+        return {int(k): float(v) for k, v in (self.logit_bias or {}).items()}
 
 
 def chat_prompt(messages: List[ChatMessage], model: str) -> Tuple[str, int]:
@@ -161,6 +183,10 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
     async def chat(request: ChatCompletionRequest):
         if not engine.is_initialized or engine.is_shutdown:
             raise HTTPException(status_code=503, detail="model not loaded")
+        bias = request.token_bias()
+        vocab = getattr(engine, "vocab_size", None)
+        if vocab is not None and bias and max(bias) >= vocab:
+            raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
         try:
             prompt, pad = chat_prompt(request.messages, request.model)
             tokens = ([0] if request.pad_zero else []) + engine.tokenizer.encode(prompt)
@@ -175,7 +201,9 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                                            frequency_penalty=request.frequency_penalty, penalty_decay=request.penalty_decay,
                                            stop_tokens=set(DEFAULT_STOP_TOKENS + stops),
                                            cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
-                                           **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}))
+                                           **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}),
+                                           **({"seed": request.seed} if request.seed is not None else {}),
+                                           **({"logit_bias": bias} if bias else {}))
         except HTTPException:
             raise
         except Exception as e:                                  # noqa: BLE001 -- app.py:231

@@ -41,8 +41,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from .core_structure import ModelLoadConfig, RequestStatus, Task
-from .samplers import is_greedy_row, sample_logits_rwkv_pip_compatible
+from .core_structure import LOGIT_BIAS_MAX, ModelLoadConfig, RequestStatus, Task
+from .samplers import is_greedy_row, sample_inverse_cdf, sample_logits_rwkv_pip_compatible
 
 
 class StateCategory(IntEnum):
@@ -165,6 +165,17 @@ class Worker:
         self.penalty_decay_tensor = torch.zeros((n, 1), dtype=torch.float16, device=dev)
         self.presence_penalty_tensor = torch.zeros((n, 1), **f32)
         self._greedy = [True] * n
+        # per-request seeds (ops.seeded_uniform): the Philox key and each slot's draw counter; host mirrors say which slots hold a
+        # seed / a logit_bias list, so that steps and installs of requests without either touch none of these tables
+        self.seeds = torch.zeros((n,), dtype=torch.int64, device=dev)
+        self.seeded = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.counters = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self._seeded = [False] * n
+        # logit_bias lists (ops.apply_logit_bias): ids / values [n, LOGIT_BIAS_MAX], entries per slot
+        self.bias_ids = torch.zeros((n, LOGIT_BIAS_MAX), dtype=torch.int32, device=dev)
+        self.bias_values = torch.zeros((n, LOGIT_BIAS_MAX), **f32)
+        self.bias_counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self._bias_n = [0] * n
         # device-side feedback of the sampled ids (run-ahead): next decode inputs and the penalty bookkeeping
         self.last_ids = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.penalty_weight = torch.ones((V,), **f32)           # occurrence increment per token id (worker.py:531)
@@ -394,6 +405,20 @@ class Worker:
         self.penalty_decay_tensor[slot, 0] = task.penalty_decay
         self.presence_penalty_tensor[slot, 0] = task.presence_penalty
         self._greedy[slot] = is_greedy_row(task.temperature, task.top_p, task.top_k)
+        # stream-ordered writes: a run-ahead row of the slot's previous request still in flight reads (and advances) the old values
+        seeded = task.seed is not None
+        if seeded or self._seeded[slot]:
+            self.seeds[slot] = ops.seed_int64(task.seed) if seeded else 0
+            self.seeded[slot] = int(seeded)
+            self.counters[slot] = 0
+            self._seeded[slot] = seeded
+        n_bias = len(task.logit_bias)
+        if n_bias or self._bias_n[slot]:
+            if n_bias:
+                self.bias_ids[slot, :n_bias] = torch.tensor(list(task.logit_bias.keys()), dtype=torch.int32)
+                self.bias_values[slot, :n_bias] = torch.tensor(list(task.logit_bias.values()), dtype=torch.float32)
+            self.bias_counts[slot] = n_bias
+            self._bias_n[slot] = n_bias
         first = task.prefill_tokens.pop(0)
         if len(task.prefill_tokens) == 0:
             cat, prefilling = StateCategory.FORWARD_ONE_DECODE, False
@@ -441,6 +466,11 @@ class Worker:
         if sampled:
             rows = self._slot_tensor(sampled)
             u = torch.rand((len(sampled),), device=self.device, dtype=torch.float32)
+            # seeded rows replace their uniform with their own Philox draw (the unseeded rows' draws stay those of the global
+            # generator, consumed exactly as before)
+            seeded_rows = [k for k, j in enumerate(sampled) if self._seeded[decode_slots[j]]]
+            if seeded_rows:
+                ops.seeded_uniform(rows, idx, self.seeds, self.seeded, self.counters, u)
         lp_rows = [j for j, s in enumerate(decode_slots) if self.state_slot[s]["task"].logprobs]
         if lp_rows:
             lp_idx = self._slot_tensor(lp_rows)
@@ -472,6 +502,8 @@ class Worker:
             for tok_id in t.forbidden_tokens:
                 logits[j, tok_id] -= 1e10
         didx = idx[:nd]
+        if any(self._bias_n[s] for s in decode_slots):     # after the forbidden tokens, before the penalties and every draw
+            ops.apply_logit_bias(logits, didx, self.bias_counts, self.bias_ids, self.bias_values)
         # penalties for every decode row + arg-max, one kernel; occurrence is decayed in place
         status_out = None
         if self._commit_kernel is not None and self.device.type == "cuda":
@@ -490,8 +522,13 @@ class Worker:
             else:
                 lrows = rows.long()
                 srows = didx.long()[lrows]
-                ids[lrows] = sample_logits_rwkv_pip_compatible(logits[lrows], self.temperature_tensor[srows],
-                                                               self.top_p_tensor[srows], self.top_k_tensor[srows]).to(torch.int32)
+                drawn = sample_logits_rwkv_pip_compatible(logits[lrows], self.temperature_tensor[srows],
+                                                          self.top_p_tensor[srows], self.top_k_tensor[srows])
+                if seeded_rows:                             # every row still drew above: the generator advances as without seeds
+                    k = torch.tensor(seeded_rows, dtype=torch.long, device=self.device)
+                    drawn[k] = sample_inverse_cdf(logits[lrows[k]], self.temperature_tensor[srows[k]], self.top_p_tensor[srows[k]],
+                                                  self.top_k_tensor[srows[k]], u[k])
+                ids[lrows] = drawn.to(torch.int32)
         self._commit_sampled(ids, didx, status_out)
         lp = None
         if lp_rows:                                         # the sampled ids are read on the device, in place

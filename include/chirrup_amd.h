@@ -493,6 +493,25 @@ int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits, const int
                          const int32_t *target_rows, float *out_lp, int32_t *out_ids, void *stream);
 
 /*
+ * Per-request seeded uniforms for the sampler (Philox4x32-10, M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9,
+ * W1 = 0xBB67AE85).  For each i < n_rows: r = rows[i], s = slot_idx[r].  When seeded[s] != 0:
+ * uniform[i] = (x0 >> 8) * 2^-24 with x0 the first word of Philox(counter = (counters[s], 0, 0, 0),
+ * key = (lo32(seeds[s]), hi32(seeds[s]))), then counters[s] += 1.  Rows whose slot is not seeded keep uniform[i].
+ * A slot appears at most once among the rows.  n_rows == 0 launches nothing; seeds must be 8-byte aligned.
+ */
+int rwkv7_seeded_uniform(int n_rows, const int32_t *rows, const int32_t *slot_idx, const uint64_t *seeds,
+                         const int32_t *seeded, uint32_t *counters, float *uniform, void *stream);
+
+/*
+ * Logit bias of n_rows rows of binary16 logits [n_rows][V], in place.  Row i uses the list of slot s = slot_idx[i] (or i):
+ * counts[s] entries (at most cap) of ids int32 [.][cap] and values binary32 [.][cap].  For each entry with 0 <= id < V and a
+ * finite logit l: logits[i][id] = fp16(clamp(float(l) + value, -65504, 65504)), one rounding; other entries are skipped and
+ * non-finite logits stay as they are.  The ids of one list must be distinct.  n_rows == 0 launches nothing.
+ */
+int rwkv7_apply_logit_bias(int n_rows, int V, int cap, void *logits, const int32_t *slot_idx, const int32_t *counts,
+                           const int32_t *ids, const float *values, void *stream);
+
+/*
  * The pieces of mm8t_seq for a decode step that folds the mm8 prologue / reduce launches into the neighbouring kernels
  * (chirrup_amd/rwkv7.py, ffn_dtype = int8): LN kernel (prologue of ffn.key, rwkv7_add_ln_mix_mm8) -> mm8t_gemm_partial ->
  * mm8_reduce_rows (corrections + relu^2 of ffn.key AND the prologue of ffn.value) -> mm8t_gemm_partial -> next LN kernel
