@@ -101,6 +101,11 @@ class Task:
     # {token id: bias}: added to the raw logits (binary32, one rounding to binary16, clamped to +-65504) after the forbidden
     # tokens and before the penalties; it moves greedy rows too, and logprobs still measure the raw output
     logit_bias: Dict[int, float] = field(default_factory=dict)
+    # prompt logprobs (None: off; k in 0..20): position i >= 1 of prefill_tokens gets the log-softmax of the raw model output after
+    # tokens < i taken at token i, plus the k most likely ids -- ("prompt_logprobs", {"start", "token_ids", "logprobs",
+    # "top_logprobs"}) messages in position order before the first token; position 0 is None.  With max_tokens=0 the request only
+    # scores: it ends (length) once the last position is known, without feeding the last prompt token or sampling anything
+    prompt_logprobs: Optional[int] = None
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -116,6 +121,10 @@ class Task:
             self.seed = _integer(self.seed, "seed")
             if not -(1 << 63) <= self.seed < (1 << 64):
                 raise ValueError("seed must be an integer in [-2^63, 2^64)")
+        if self.prompt_logprobs is not None:
+            self.prompt_logprobs = _integer(self.prompt_logprobs, "prompt_logprobs")
+            if not 0 <= self.prompt_logprobs <= 20:
+                raise ValueError("prompt_logprobs must be None or in 0..20")
         bias = dict(self.logit_bias or {})
         if len(bias) > LOGIT_BIAS_MAX:
             raise ValueError(f"logit_bias holds {len(bias)} entries, at most {LOGIT_BIAS_MAX} are allowed")

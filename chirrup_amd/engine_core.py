@@ -217,7 +217,7 @@ class AsyncEngineCore:
                    max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], task_id: Optional[str] = None,
                    cache_prefill: bool = False, cache_prefill_padding: int = 0,
                    return_logits: bool = False, logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
-                   logit_bias: Optional[Dict[int, float]] = None) -> AsyncEngineCompletion:
+                   logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None) -> AsyncEngineCompletion:
         assert not (state is not None and prefill_tokens is None), "prefill_tokens cannot be None when state is not None"
         if not self.is_initialized:
             raise RuntimeError("Engine not initialized")
@@ -242,7 +242,7 @@ class AsyncEngineCore:
                                      stop_tokens=stop_tokens, forbidden_tokens=forbidden_tokens, max_tokens=max_tokens,
                                      cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                                      return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
-                                     logit_bias=logit_bias)
+                                     logit_bias=logit_bias, prompt_logprobs=prompt_logprobs)
 
     def _on_worker_fatal(self, worker, exc) -> None:
         """Called on a dying worker's thread.  When it was the last live worker, nobody will ever pick up the

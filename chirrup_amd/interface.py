@@ -1,7 +1,8 @@
 """Per-request handle of the engine façade (boundary B4).
 
 Same surface as the reference's chirrup/interface.py:31-142: an async iterator over
-("token", id, text[, logits[, logprobs]]) / ("cache_prefill", {"state", "prefilled_tokens"}) events, lazily
+("token", id, text[, logits[, logprobs]]) / ("cache_prefill", {"state", "prefilled_tokens"}) / ("prompt_logprobs", {"start",
+"token_ids", "logprobs", "top_logprobs"}) events, lazily
 submitting its Task on first iteration, with ``get_full_completion()`` and ``abort()``."""
 import asyncio
 import queue
@@ -21,7 +22,7 @@ class AsyncEngineCompletion:
                  max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], cache_prefill: bool = False,
                  cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None,
                  logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
-                 logit_bias: Optional[Dict[int, float]] = None):
+                 logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None):
         self.task_id = task_id
         # the worker polls it for ("abort", None); a process-mode engine passes a channel that reaches the worker's process
         self.task_event_queue = task_event_queue if task_event_queue is not None else queue.Queue()
@@ -33,7 +34,7 @@ class AsyncEngineCompletion:
                          stop_tokens=stop_tokens, forbidden_tokens=list(forbidden_tokens or []),
                          cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                          return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
-                         logit_bias=dict(logit_bias or {}))
+                         logit_bias=dict(logit_bias or {}), prompt_logprobs=prompt_logprobs)
         self._task_queue = task_queue
         self._submitted = False
         self.is_finished = False
@@ -59,6 +60,8 @@ class AsyncEngineCompletion:
                 return ("token", *payload)
             if kind == "cache_prefill":
                 return ("cache_prefill", payload)
+            if kind == "prompt_logprobs":
+                return ("prompt_logprobs", payload)
             if kind == "task_completed":
                 self.is_finished = True
                 self.task = payload

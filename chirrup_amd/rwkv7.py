@@ -220,6 +220,7 @@ class _LazyWeights(dict):
 # Library-GEMM forms of a forward of more than 256 token rows
 _SPLIT_ROWS_MIN = 1024      # from this many rows R/K/V as three GEMMs (1.15 PFLOP/s) instead of one batched launch (1.0)
 _TUNE_MM_MIN_ROWS = 512     # from this many rows _mm_nt measures its formulation (below: the single call always won the sweep)
+HEAD_ROWS_BLOCK = 512       # rows per head call of forward_slots(logit_rows=...): 64 MB of fp16 logits at V = 65536
 
 
 class _Plan(NamedTuple):
@@ -650,11 +651,15 @@ class RWKV_x070:
         x = F.layer_norm(x, (self.n_embd,), weight=z["ln_out.weight"], bias=z["ln_out.bias"])
         return F.linear(x, z["head.weight"])
 
-    def forward_slots(self, idxs, pool, slot_idx: torch.Tensor, full_output: bool = False, feedback=None, zero_sync: bool = False):
+    def forward_slots(self, idxs, pool, slot_idx: torch.Tensor, full_output: bool = False, feedback=None, zero_sync: bool = False,
+                      logit_rows: Optional[torch.Tensor] = None, row_sink: Optional[Callable] = None):
         """State-pool form of forward_seq_batch_seperate (not in the reference): ``pool`` is the
         worker's WHOLE slot table [fp16[L,2,n,C], fp16[L,n,H,64,64], int32[n]] and batch row b lives
         in slot ``slot_idx[b]`` (int32 [B] on the device, all distinct).  Nothing is gathered or
-        swapped: the kernels address the slot tables directly (SURVEY.md section 8f "next 1")."""
+        swapped: the kernels address the slot tables directly (SURVEY.md section 8f "next 1").
+        logit_rows: int32 [R] on the device, ascending flattened token rows b*T + t: the call then returns (logits, head output of
+        those rows, fp16 [R, V]) -- or, with row_sink, calls row_sink(r0, block) for consecutive blocks of at most
+        HEAD_ROWS_BLOCK rows in order and returns (logits, None), so that a chunk's rows never exist all at once (prompt logprobs)."""
         if not self.fused:
             raise ops._lib.ChirrupAmdError("forward_slots needs the fused HIP path (a GPU)")
         if isinstance(idxs, torch.Tensor):
@@ -665,9 +670,16 @@ class RWKV_x070:
         # one launch: the embedding rows (a negative token takes feedback[its slot], the id the sampler left there), the slots'
         # step counters in row order and, for a decode graph, the zeroing of the stream's launch-sync words
         x, elapsed_rows = ops.embed_rows(self.z["emb.weight"], tok.contiguous(), slot_idx, feedback, zero_sync, elapsed_pool=pool[2])
-        return self._forward_embedded_fused(x, pool, tok.shape[1], full_output, slot_idx=slot_idx, elapsed_rows=elapsed_rows)
+        if logit_rows is None:
+            return self._forward_embedded_fused(x, pool, tok.shape[1], full_output, slot_idx=slot_idx, elapsed_rows=elapsed_rows)
+        if full_output:
+            raise ValueError("logit_rows and full_output are exclusive")
+        if logit_rows.dtype != torch.int32 or logit_rows.dim() != 1 or logit_rows.device != self.device:
+            raise ops._lib.ChirrupAmdError("logit_rows: expected int32 [R] on the model's device")
+        return self._forward_embedded_fused(x, pool, tok.shape[1], False, slot_idx=slot_idx, elapsed_rows=elapsed_rows,
+                                            logit_rows=(logit_rows, row_sink))
 
-    def _forward_embedded_fused(self, x, state, T, full_output, slot_idx=None, elapsed_rows=None):
+    def _forward_embedded_fused(self, x, state, T, full_output, slot_idx=None, elapsed_rows=None, logit_rows=None):
         """_forward_embedded's arithmetic as plan_forward dispatches it: every element-wise chain in one HIP kernel (csrc/elementwise.hip,
         csrc/wkv7.hip), in the decode regime every projection through the MFMA ring GEMM (csrc/skinny_gemm.hip).  x [B,T,C] is consumed."""
         s0, s1, s2 = state
@@ -687,6 +699,8 @@ class RWKV_x070:
             self._tmix_core(p, f, i, lw, rkv, up, s1[i])
             self._att_output(p, f, lw, s0[i][1], w_O)
             self._channel_mix(p, f, lw, w_fK, w_fV)
+        if logit_rows is not None:
+            return self._ln_out_rows(p, f, s2, *logit_rows)
         return self._ln_out_head(p, f, full_output, s2)
 
     def _fused_buffers(self, p: _Plan, x, T, s0, slot_idx, elapsed):
@@ -905,12 +919,58 @@ class RWKV_x070:
             ops.advance_elapsed(s2, T, f.slot_idx)              # state[2] += T over the slot list, one launch
         if p.head == "mm8":
             return ops.mm8t_linear(xo.reshape(-1, C), *self.head8, tiled=self._head8_tiled).view(*xo.shape[:-1], -1)
-        if p.head == "ring":
-            if self._head_t is None:
-                hwt = z["head.weight"]
-                self._head_t = ops.tile_weight(hwt) if (self.tiled_weights and hwt.shape[0] % 128 == 0 and hwt.shape[1] % 64 == 0) else hwt
-            return ops.skinny_linear(xo, self._head_t, splits=1)
+        if p.head == "ring":                            # (full_output: [B, T, C] rows as one [B*T, C] operand)
+            return ops.skinny_linear(xo.reshape(-1, C), self._head_ring(), splits=1).view(*xo.shape[:-1], -1)
         return F.linear(xo, z["head.weight"])          # (a tile-image-only model rebuilds it: _LazyWeights)
+
+    def _head_ring(self):
+        if self._head_t is None:
+            hwt = self.z["head.weight"]
+            self._head_t = ops.tile_weight(hwt) if (self.tiled_weights and hwt.shape[0] % 128 == 0 and hwt.shape[1] % 64 == 0) else hwt
+        return self._head_t
+
+    def _head_rows(self, x2: torch.Tensor) -> torch.Tensor:
+        """Head output fp16 [r, V] of r <= HEAD_ROWS_BLOCK ln_out rows, one fixed formulation per case (no timing): uint8 head
+        -> mm8t_linear in blocks of <= 256 rows (a larger call would take the dequantising scratch path); <= 256 rows, or no
+        resident row-major head -> the ring kernel in blocks of <= 256 rows; else one library call."""
+        r = x2.shape[0]
+        if self.head8 is not None or r <= 256 or not self.keep_row_major:
+            parts = []
+            for r0 in range(0, r, 256):
+                blk = x2[r0:r0 + 256]
+                parts.append(ops.mm8t_linear(blk, *self.head8, tiled=self._head8_tiled) if self.head8 is not None else
+                             ops.skinny_linear(blk, self._head_ring(), splits=1))
+            return parts[0] if len(parts) == 1 else torch.cat(parts)
+        return F.linear(x2, self.z["head.weight"])
+
+    def _ln_out_rows(self, p: _Plan, f, s2, rows: torch.Tensor, row_sink):
+        """_ln_out_head for a forward that also wants the head output of chosen token rows: ln_out over ALL B*T rows (the
+        full_output route: one add_ln_mix), then the last token of each sequence through the plan's head -- the returned logits --
+        and the chosen rows gathered and through _head_rows, HEAD_ROWS_BLOCK rows at a time."""
+        z, B, T, C = self.z, f.B, f.T, f.C
+        xo = f.new(B, T, C)
+        ops.add_ln_mix(B, T, C, f.x, f.delta, None, z["ln_out.weight"], z["ln_out.bias"], 1e-5, None, None,
+                       None, xo, delta_partials=f.dparts, mm8_in=f.dq)
+        if f.slot_idx is not None:
+            ops.advance_elapsed(s2, T, f.slot_idx)
+        last = xo[:, -1, :].contiguous()
+        if p.head == "mm8":
+            out = ops.mm8t_linear(last, *self.head8, tiled=self._head8_tiled)
+        elif p.head == "ring":
+            out = ops.skinny_linear(last, self._head_ring(), splits=1)
+        else:
+            out = F.linear(last, z["head.weight"])
+        x2, R = xo.view(B * T, C), rows.numel()
+        blocks = []
+        for r0 in range(0, R, HEAD_ROWS_BLOCK):
+            blk = self._head_rows(x2.index_select(0, rows[r0:r0 + HEAD_ROWS_BLOCK].long()))
+            if row_sink is not None:
+                row_sink(r0, blk)
+            else:
+                blocks.append(blk)
+        if row_sink is not None:
+            return out, None
+        return out, (torch.cat(blocks) if len(blocks) != 1 else blocks[0]) if blocks else torch.empty((0, out.shape[1]), dtype=DTYPE, device=out.device)
 
     def _tmix(self, layer_id, lw: _Layer, x, x_prev, v_first, S, elapsed_t):
         """Time-mix block, arithmetic of RWKV_x070_TMix_seq_batch (rwkv7.py:618-649).

@@ -4,6 +4,8 @@ api_model.py:8-112, chirrup/utils/prompt_formatters.py, streaming_string_parser.
 fields, chat template (`User:/Assistant:` paragraphs, model suffixes `:thinking` / `:no-thinking`), `[0]` + encode,
 prefix-state cache protocol (`check_and_wait_prefill` -> `completion(state=...)` -> `cache()` + `awake_hang_up_prefills` on the
 ("cache_prefill", ...) event; in process mode the states are arena row addresses and never leave HBM) and 10-s keep-alive comments.
+`POST /v1/completions` is OpenAI's legacy text route (not in the reference): raw prompts, and with `echo` + `logprobs` the scores of
+the prompt's own tokens (prompt logprobs, `max_tokens=0` to score only) -- what evaluation harnesses call.
 Not here: the settings CLI and the batch translate / rollout routes (out of scope).
 
     app = create_app(engine, state_cache_size=50)       # engine: an initialised AsyncEngineCore
@@ -19,7 +21,7 @@ from fastapi import FastAPI, HTTPException
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, model_validator
 
-from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, LOGIT_BIAS_MAX
+from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, LOGIT_BIAS_MAX, RequestStatus
 from .state_cache import SimpleStateCache
 
 KEEP_ALIVE_S = 10.0
@@ -30,6 +32,20 @@ class ChatMessage(BaseModel):
     role: str
     content: str
     reasoning_content: Optional[str] = None
+
+
+def _check_logit_bias(logit_bias: Optional[Dict[str, float]]) -> None:
+    seen = set()
+    for key, value in (logit_bias or {}).items():
+        if not re.fullmatch(r"[0-9]+", key):
+            raise ValueError(f"logit_bias: key {key!r} is not a token id")
+        if int(key) in seen:
+            raise ValueError(f"logit_bias: token id {int(key)} appears twice")
+        seen.add(int(key))
+        if not -100.0 <= value <= 100.0:
+            raise ValueError(f"logit_bias: the bias of token {key} is outside [-100, 100]")
+    if len(seen) > LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries")
 
 
 class ChatCompletionRequest(BaseModel):                      # api_model.py:14-62: same fields, defaults and ranges
@@ -63,21 +79,67 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
 
     @model_validator(mode="after")
     def _logit_bias_entries(self):
-        seen = set()
-        for key, value in (self.logit_bias or {}).items():
-            if not re.fullmatch(r"[0-9]+", key):
-                raise ValueError(f"logit_bias: key {key!r} is not a token id")
-            if int(key) in seen:
-                raise ValueError(f"logit_bias: token id {int(key)} appears twice")
-            seen.add(int(key))
-            if not -100.0 <= value <= 100.0:
-                raise ValueError(f"logit_bias: the bias of token {key} is outside [-100, 100]")
-        if len(seen) > LOGIT_BIAS_MAX:
-            raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries")
+        _check_logit_bias(self.logit_bias)
         return self
 
     def token_bias(self) -> Dict[int, float]:
         return {int(k): float(v) for k, v in (self.logit_bias or {}).items()}
+
+
+class CompletionRequest(BaseModel):
+    """OpenAI's legacy completions request.  prompt: a string, a token-id list, or a list of either (one choice per prompt);
+    logprobs (0..20): the log-probability of every returned token and that many alternatives; echo: the prompt comes back in front
+    of the generated text, with its own logprobs when logprobs is set (max_tokens=0 then only scores the prompt).  The sampling
+    fields have the chat route's defaults and ranges; n and best_of above 1 are not supported."""
+    model: str = "rwkv-latest"
+    prompt: Union[str, List[int], List[Union[str, List[int]]]]
+    max_tokens: int = Field(default=16, ge=0)
+    echo: bool = False
+    logprobs: Optional[int] = Field(None, ge=0, le=20)
+    stream: bool = False
+    stop: Optional[Union[str, List[str]]] = None
+    temperature: float = Field(default=DEFAULT_SAMPLING_CONFIG["temperature"], ge=0.0, le=2.0)
+    top_p: float = Field(default=DEFAULT_SAMPLING_CONFIG["top_p"], ge=0.0, le=1.0)
+    presence_penalty: float = Field(default=DEFAULT_SAMPLING_CONFIG["presence_penalty"], ge=0, le=2.0)
+    frequency_penalty: float = Field(default=DEFAULT_SAMPLING_CONFIG["frequency_penalty"], ge=0, le=2.0)
+    penalty_decay: float = Field(default=DEFAULT_SAMPLING_CONFIG["penalty_decay"], ge=0.0, le=1.0)
+    seed: Optional[int] = Field(None, ge=-(1 << 63), lt=1 << 64)
+    logit_bias: Optional[Dict[str, float]] = None
+    pad_zero: bool = True
+    use_state_cache: bool = True
+    cache_prefill: bool = True
+    n: int = 1
+    best_of: Optional[int] = None
+
+    @model_validator(mode="after")
+    def _fields(self):
+        if self.max_tokens == 0 and not self.echo:
+            raise ValueError("max_tokens=0 needs echo")
+        if isinstance(self.prompt, list) and len(self.prompt) == 0:
+            raise ValueError("prompt is empty")
+        _check_logit_bias(self.logit_bias)
+        return self
+
+    def prompts(self) -> List[Union[str, List[int]]]:
+        p = self.prompt
+        if isinstance(p, str) or (p and all(isinstance(x, int) for x in p)):
+            return [p]
+        return list(p)
+
+    def token_bias(self) -> Dict[int, float]:
+        return {int(k): float(v) for k, v in (self.logit_bias or {}).items()}
+
+
+def legacy_top(idx2token: Dict[int, bytes], top) -> Optional[Dict[str, float]]:
+    """One position's top_logprobs in the legacy format: {token string: logprob}; of ids with the same string the higher wins."""
+    if top is None:
+        return None
+    out: Dict[str, float] = {}
+    for i, v in top:
+        key = idx2token.get(i, b"").decode("utf-8", errors="backslashreplace")
+        if key not in out or v > out[key]:
+            out[key] = v
+    return out
 
 
 def chat_prompt(messages: List[ChatMessage], model: str) -> Tuple[str, int]:
@@ -276,7 +338,165 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
 
         return StreamingResponse(body(), media_type="text/event-stream" if request.stream else "application/json", headers=_SSE_HEADERS)
 
+    def tok_str(i: int) -> str:
+        return idx2token.get(i, b"").decode("utf-8", errors="backslashreplace")
+
+    def legacy_logprobs(entries, offset: int) -> Dict[str, Any]:
+        """entries: (token id, logprob or None, top [(id, logprob)] or None) -> the legacy logprobs object; text_offset counts the
+        token strings from `offset`."""
+        out: Dict[str, Any] = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+        for tok, lp, top in entries:
+            s_ = tok_str(tok)
+            out["tokens"].append(s_)
+            out["token_logprobs"].append(lp)
+            out["top_logprobs"].append(legacy_top(idx2token, top))
+            out["text_offset"].append(offset)
+            offset += len(s_)
+        return out
+
+    @app.post("/v1/completions")
+    async def completions(request: CompletionRequest):
+        if not engine.is_initialized or engine.is_shutdown:
+            raise HTTPException(status_code=503, detail="model not loaded")
+        if request.n != 1 or (request.best_of is not None and request.best_of != 1):
+            raise HTTPException(status_code=400, detail="n and best_of other than 1 are not supported")
+        bias = request.token_bias()
+        vocab = getattr(engine, "vocab_size", None)
+        if vocab is not None and bias and max(bias) >= vocab:
+            raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        k, skip = request.logprobs, (1 if request.pad_zero else 0)      # skip: the token 0 in front is fed, not echoed
+        score_prompt = request.echo and k is not None
+        try:
+            items = []
+            for p in request.prompts():
+                ids = engine.tokenizer.encode(p) if isinstance(p, str) else list(p)
+                if any(not 0 <= t < (vocab if vocab is not None else 1 << 62) for t in ids):
+                    raise HTTPException(status_code=400, detail="prompt: a token id is outside the vocabulary")
+                toks = [0] * skip + ids
+                if not toks:
+                    raise HTTPException(status_code=400, detail="prompt is empty")
+                text = (p if isinstance(p, str) else b"".join(idx2token.get(t, b"") for t in ids).decode("utf-8", errors="replace")
+                        if idx2token else engine.tokenizer.decode(ids, utf8_errors="replace"))
+                items.append((toks, text))
+            stops: List[int] = []
+            for word in ([request.stop] if isinstance(request.stop, str) else (request.stop or [])):
+                stops.extend(engine.tokenizer.encode(word))
+        except HTTPException:
+            raise
+        except Exception as e:                                  # noqa: BLE001
+            raise HTTPException(status_code=500, detail=f"generation failed: {e}")
+        cid, created_at = f"cmpl-{uuid.uuid4().hex}", int(time.time())
+        # every prompt position must be fed to be scored: no prefix-state cache lookup then (the state may still be exported)
+        use_cache = state_cache is not None and request.use_state_cache and not score_prompt
+        completions_: List[Any] = []
+        cached: Dict[int, int] = {}                             # choice index -> prompt tokens covered by a cached state
+
+        def sse(index: int, text: str, logprobs=None, finish=None) -> str:
+            body = {"id": cid, "object": "text_completion", "created": created_at, "model": request.model,
+                    "choices": [{"text": text, "index": index, "logprobs": logprobs, "finish_reason": finish}]}
+            return f"data: {json.dumps(body, ensure_ascii=False)}\n\n"
+
+        async def one(index: int, toks: List[int], text: str, q: asyncio.Queue) -> Dict[str, Any]:
+            echo_text = text if request.echo else ""
+            if request.max_tokens == 0 and not score_prompt:     # echo alone: nothing to compute
+                if request.stream:
+                    q.put_nowait(sse(index, echo_text, None, "length"))
+                return {"text": echo_text, "index": index, "logprobs": None, "finish_reason": "length", "n_out": 0}
+            rest, state, n_cached = toks, None, 0
+            if use_cache:
+                rest, state, n_cached = await state_cache.check_and_wait_prefill(toks, 0)
+            cached[index] = n_cached
+            comp = engine.completion(prompt_str=text, prefill_tokens=rest, state=state, temperature=request.temperature,
+                                     top_p=request.top_p, max_tokens=request.max_tokens, presence_penalty=request.presence_penalty,
+                                     frequency_penalty=request.frequency_penalty, penalty_decay=request.penalty_decay,
+                                     stop_tokens=set(DEFAULT_STOP_TOKENS + stops),
+                                     cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=0,
+                                     **({"logprobs": True, "top_logprobs": k} if k is not None and request.max_tokens > 0 else {}),
+                                     **({"prompt_logprobs": k} if score_prompt else {}),
+                                     **({"seed": request.seed} if request.seed is not None else {}),
+                                     **({"logit_bias": bias} if bias else {}))
+            completions_.append(comp)
+            plp: List[Any] = [None] * len(toks)
+            n_plp, gen, gen_text = 0, [], []
+            sent_head = False
+            if request.echo and not score_prompt and request.stream:
+                q.put_nowait(sse(index, echo_text))
+                sent_head = True
+            async for ev in comp:
+                if ev[0] == "prompt_logprobs":
+                    pl = ev[1]
+                    for j, (t, v, top) in enumerate(zip(pl["token_ids"], pl["logprobs"], pl["top_logprobs"])):
+                        plp[pl["start"] + j] = (t, v, top)
+                    n_plp = pl["start"] + len(pl["logprobs"])
+                    if request.stream and n_plp == len(toks) and not sent_head:
+                        q.put_nowait(sse(index, echo_text, legacy_logprobs(plp[skip:], 0)))
+                        sent_head = True
+                elif ev[0] == "token":
+                    lp = ev[4] if len(ev) > 4 else None
+                    gen.append((ev[1], lp["logprob"] if lp else None, lp["top_logprobs"] if lp else None))
+                    gen_text.append(ev[2])
+                    if request.stream:
+                        offset = len(echo_text) + sum(len(tok_str(t)) for t, _, _ in gen[:-1])
+                        q.put_nowait(sse(index, ev[2], legacy_logprobs(gen[-1:], offset) if k is not None else None))
+                elif ev[0] == "cache_prefill" and state_cache is not None:
+                    key = tuple(toks[:n_cached]) + tuple(ev[1]["prefilled_tokens"])
+                    node = state_cache.cache(key, ev[1]["state"], return_trie_node=True)
+                    if node is not None:
+                        await state_cache.awake_hang_up_prefills(key)
+            reason = RequestStatus.get_finished_reason(comp.task.request_status)
+            finish = str(reason) if reason is not None else "stop"
+            logprobs = None
+            if k is not None:
+                entries = ([e for e in plp[skip:]] if score_prompt else []) + gen
+                logprobs = legacy_logprobs(entries, 0 if score_prompt else len(echo_text))
+            if request.stream:
+                q.put_nowait(sse(index, "", None, finish))
+            return {"text": echo_text + "".join(gen_text), "index": index, "logprobs": logprobs, "finish_reason": finish,
+                    "n_out": len(comp.task.generated_tokens)}
+
+        async def produce(q: asyncio.Queue):
+            try:
+                choices = await asyncio.gather(*[one(i, toks, text, q) for i, (toks, text) in enumerate(items)])
+                if request.stream:
+                    q.put_nowait("data: [DONE]\n\n")
+                else:
+                    n_in, n_out = sum(len(t) for t, _ in items), sum(c.pop("n_out") for c in choices)
+                    q.put_nowait(json.dumps({"id": cid, "object": "text_completion", "created": created_at, "model": request.model,
+                                             "choices": choices,
+                                             "usage": {"prompt_tokens": n_in, "completion_tokens": n_out, "total_tokens": n_in + n_out}},
+                                            ensure_ascii=False))
+            except Exception as e:                              # noqa: BLE001 -- reported in-band, as on the chat route
+                err = json.dumps({"error": {"message": str(e), "type": "internal_error"}})
+                q.put_nowait(f"data: {err}\n\ndata: [DONE]\n\n" if request.stream else err)
+            q.put_nowait(None)
+
+        async def body():
+            q: asyncio.Queue = asyncio.Queue()
+            task = asyncio.create_task(produce(q))
+            try:
+                while True:
+                    try:
+                        item = await asyncio.wait_for(q.get(), timeout=KEEP_ALIVE_S)
+                    except asyncio.TimeoutError:
+                        if request.stream:
+                            yield ":\n\n"
+                        continue
+                    if item is None:
+                        return
+                    yield item
+            finally:
+                task.cancel()
+                for c in completions_:
+                    c.abort()
+                if use_cache:
+                    for i, n_cached in cached.items():
+                        toks = items[i][0]
+                        if n_cached != len(toks):
+                            await state_cache.awake_hang_up_prefills(tuple(toks))
+
+        return StreamingResponse(body(), media_type="text/event-stream" if request.stream else "application/json", headers=_SSE_HEADERS)
+
     return app
 
 
-__all__ = ["create_app", "ChatCompletionRequest", "ChatMessage", "ThinkSplitter", "chat_prompt"]
+__all__ = ["create_app", "ChatCompletionRequest", "ChatMessage", "CompletionRequest", "ThinkSplitter", "chat_prompt"]

@@ -75,9 +75,11 @@ def min_swaps_to_target_fast(lst, elements):
 
 
 def _empty_slot() -> dict:
+    # feedback: the slot's next decode input is last_ids[slot] on the device.  Prompt logprobs (task.prompt_logprobs set):
+    # plp_prompt = the tokens as admitted, plp_next = index of the next one to feed, plp_sent = positions already sent
     return {"task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
             "state_category": StateCategory.EMPTY, "prefilled_tokens": [], "prefill_cached": False,
-            "feedback": False}      # feedback: the slot's next decode input is last_ids[slot] on the device
+            "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0}
 
 
 class Worker:
@@ -252,6 +254,7 @@ class Worker:
             td["state_category"] = StateCategory.FORWARD_ONE_PREFILL
         if len(t.prefill_tokens) == 0:
             td["state_category"], td["is_prefilling"] = StateCategory.FORWARD_ONE_DECODE, False
+            self._maybe_end_scoring(td)
         elif len(t.prefill_tokens) < self.min_forward_seq_len:
             td["state_category"] = StateCategory.FORWARD_ONE_PREFILL
 
@@ -262,6 +265,23 @@ class Worker:
         if len(t.prefill_tokens) == 0:
             td["is_prefilling"], td["state_category"] = False, StateCategory.FORWARD_ONE_DECODE
         self._maybe_cache_prefill(td, slot)
+        if len(t.prefill_tokens) == 0:
+            self._maybe_end_scoring(td)
+
+    @staticmethod
+    def _scoring_only(t: Task) -> bool:
+        return t.prompt_logprobs is not None and t.max_tokens == 0
+
+    def _maybe_end_scoring(self, td):
+        """A scoring-only request (prompt_logprobs, max_tokens=0) whose next input is its last prompt token: that token is never
+        fed.  It ends (length) now if every prompt position has been sent, else it waits suspended for the forward in flight."""
+        t: Task = td["task"]
+        if not self._scoring_only(t):
+            return
+        if td["plp_sent"] >= len(td["plp_prompt"]):
+            t.request_status = RequestStatus.FINISHED_LENGTH_CAPPED
+        else:
+            td["state_category"] = StateCategory.FORWARD_ONE_SUSPENDED
 
     def _handle_forward_one_decode_phase(self, td, tok: int, raw_logits=None, logprobs=None):
         """One sampled token of a live request (chirrup/worker.py:503-560): stop / length checks, text, message.
@@ -308,9 +328,17 @@ class Worker:
         is gone (finished or aborted while this forward was in flight) are dropped."""
         if rec is None:
             return
+        if isinstance(rec, list):                           # the records of one step: its single-token forward, then its chunk
+            for r in rec:
+                self._handle_results(r)
+            return
         if rec["event"] is not None:
             rec["event"].synchronize()
+        if rec.get("plp") is not None:
+            self._handle_prompt_logprobs(rec["plp"])
         n_rows = len(rec["rows"])
+        if n_rows == 0:
+            return
         host_ids = rec["ids"][: n_rows + (1 if rec.get("status") else 0)].tolist()        # ONE device->host copy for the whole batch
         if rec.get("status") and host_ids[n_rows] != 0:
             # the time-mix launch's bounded in-launch waits (include/chirrup_amd.h: rwkv7_tmix_gemms): a wait that gave up left the LoRA
@@ -334,6 +362,67 @@ class Worker:
             if RequestStatus.is_finished(task.request_status):
                 done.append(slot)
         self._process_accomplished_tasks(done)
+
+    def _handle_prompt_logprobs(self, plp):
+        """Send the prompt positions one forward computed: plp = (entries, lp [R, 1 + k], ids [R, k]) on the host, entries
+        (slot, task, first position, first row, rows).  Rows of a request that has ended meanwhile (abort; the slot may hold a new
+        request) are dropped."""
+        entries, lp, ids = plp
+        lp, ids = lp.tolist(), ids.tolist()
+        done = []
+        for slot, task, pos, r0, n in entries:
+            td = self.state_slot[slot]
+            if td["task"] is not task or RequestStatus.is_finished(task.request_status):
+                continue
+            k, prompt = task.prompt_logprobs, td["plp_prompt"]
+            vals = [v[0] for v in lp[r0:r0 + n]]
+            tops = [list(zip(i[:k], v[1:1 + k])) for i, v in zip(ids[r0:r0 + n], lp[r0:r0 + n])]
+            if pos == 1:                                    # position 0 has no logprob
+                pos, vals, tops = 0, [None] + vals, [None] + tops
+            task.output_queue.put_nowait(("prompt_logprobs", {"start": pos, "token_ids": prompt[pos:pos + len(vals)],
+                                                              "logprobs": vals, "top_logprobs": tops}))
+            td["plp_sent"] = pos + len(vals)
+            if td["state_category"] == StateCategory.FORWARD_ONE_SUSPENDED and td["plp_sent"] >= len(prompt):
+                task.request_status = RequestStatus.FINISHED_LENGTH_CAPPED
+                done.append(slot)
+        self._process_accomplished_tasks(done)
+
+    def _prompt_rows(self, asks, T: int):
+        """Flattened rows b*T + t and their targets (the next prompt token) for the asking batch rows `asks` = [(b, slot)] of a
+        forward of T tokens per sequence; advances each slot's prompt cursor.  Returns (rows, targets, entries)."""
+        rows, targets, entries = [], [], []
+        for b, s in asks:
+            td = self.state_slot[s]
+            nxt, prompt = td["plp_next"], td["plp_prompt"]
+            entries.append((s, td["task"], nxt + 1, len(rows), T))
+            rows.extend(range(b * T, b * T + T))
+            targets.extend(prompt[nxt + 1:nxt + 1 + T])
+            td["plp_next"] = nxt + T
+        return rows, targets, entries
+
+    def _upload_int32(self, *lists):
+        """One host->device copy of int32 lists (pinned and non-blocking on a GPU: no synchronisation); returns device views."""
+        flat = [v for lst in lists for v in lst]
+        cuda = self.device.type == "cuda"
+        host = torch.tensor(flat, dtype=torch.int32)
+        if cuda:
+            host = host.pin_memory()
+        dev = host.to(self.device, non_blocking=True)
+        out, o = [], 0
+        for lst in lists:
+            out.append(dev[o:o + len(lst)])
+            o += len(lst)
+        return out
+
+    def _download_plp(self, entries, lp, ids):
+        """The prompt-logprob part of a record: device results copied into pinned host memory behind the record's event."""
+        if self.device.type != "cuda":
+            return (entries, lp, ids)
+        hv = torch.empty(lp.shape, dtype=lp.dtype, pin_memory=True)
+        hi = torch.empty(ids.shape, dtype=ids.dtype, pin_memory=True)
+        hv.copy_(lp, non_blocking=True)
+        hi.copy_(ids, non_blocking=True)
+        return (entries, hv, hi)
 
     def _process_accomplished_tasks(self, slots):
         for s in slots:
@@ -419,6 +508,14 @@ class Worker:
                 self.bias_values[slot, :n_bias] = torch.tensor(list(task.logit_bias.values()), dtype=torch.float32)
             self.bias_counts[slot] = n_bias
             self._bias_n[slot] = n_bias
+        plp_prompt = list(task.prefill_tokens) if task.prompt_logprobs is not None else None
+        if plp_prompt is not None and len(plp_prompt) == 1:      # its one position has no logprob: sent at once
+            task.output_queue.put_nowait(("prompt_logprobs", {"start": 0, "token_ids": list(plp_prompt), "logprobs": [None],
+                                                              "top_logprobs": [None]}))
+            if self._scoring_only(task):
+                task.request_status = RequestStatus.FINISHED_LENGTH_CAPPED
+                task.output_queue.put_nowait(("task_completed", task))
+                return
         first = task.prefill_tokens.pop(0)
         if len(task.prefill_tokens) == 0:
             cat, prefilling = StateCategory.FORWARD_ONE_DECODE, False
@@ -427,7 +524,8 @@ class Worker:
         else:
             cat, prefilling = StateCategory.FORWARD_SEQ, True
         td = _empty_slot()
-        td.update(task=task, is_prefilling=prefilling, next_input_token=first, state_category=cat)
+        td.update(task=task, is_prefilling=prefilling, next_input_token=first, state_category=cat, plp_prompt=plp_prompt,
+                  plp_sent=1 if plp_prompt is not None and len(plp_prompt) == 1 else 0)
         self.state_slot[slot] = td
 
     def _organize_batch(self):
@@ -472,6 +570,12 @@ class Worker:
             if seeded_rows:
                 ops.seeded_uniform(rows, idx, self.seeds, self.seeded, self.counters, u)
         lp_rows = [j for j, s in enumerate(decode_slots) if self.state_slot[s]["task"].logprobs]
+        # single-token prefill rows that ask for prompt logprobs: their row list and targets, uploaded before the forward
+        p_asks = [(nd + j, s) for j, s in enumerate(prefill_slots) if self.state_slot[s]["plp_prompt"] is not None]
+        if p_asks:
+            p_k = max(self.state_slot[s]["task"].prompt_logprobs for _, s in p_asks)
+            p_rows, p_targets, p_entries = self._prompt_rows(p_asks, 1)
+            p_rows_dev, p_targets_dev = self._upload_int32(p_rows, p_targets)
         if lp_rows:
             lp_idx = self._slot_tensor(lp_rows)
             lp_k = max(self.state_slot[decode_slots[j]]["task"].top_logprobs for j in lp_rows)
@@ -488,8 +592,20 @@ class Worker:
             tok = torch.where(tok < 0, self.last_ids[idx.long()].long().view(-1, 1), tok)
             out = self.model.forward_slots(tok, self.batch_state, idx)
         self._launches += 1
+        plp = None
+        if p_asks:
+            # out[nd:] are the prefill rows: the penalties, bias and forbidden tokens below edit out[:nd] only, and this launch runs
+            # before the next forward can overwrite a graph's static output buffer
+            pv, pi = ops.token_logprobs(out, p_k, targets=p_targets_dev, rows=p_rows_dev)
+            plp = self._download_plp(p_entries, pv, pi)
         if nd == 0:
-            return None
+            if plp is None:
+                return None
+            event = None
+            if self.device.type == "cuda":
+                event = torch.cuda.Event()
+                event.record()
+            return {"rows": [], "ids": None, "event": event, "raw": {}, "status": False, "plp": plp}
         logits = out[:nd]
         # logprobs are those of the raw model output: the rows that ask are copied before the forbidden tokens and the penalty
         # kernel edit `logits` in place (the graph's output buffer is static)
@@ -557,6 +673,8 @@ class Worker:
                "status": status_out is not None and self._ids_host is not None}
         if lp is not None:
             rec["lp"] = lp
+        if plp is not None:
+            rec["plp"] = plp
         return rec
 
     def _graph_for(self, n: int):
@@ -578,6 +696,10 @@ class Worker:
                 for s in seq_slots]
         n_tok = min(self.max_forward_seq_len_per_forward, *lens)
         assert n_tok > 0
+        asks = [(b, s) for b, s in enumerate(seq_slots) if self.state_slot[s]["plp_prompt"] is not None]
+        if asks:                                            # (before the cursors below move)
+            k = max(self.state_slot[s]["task"].prompt_logprobs for _, s in asks)
+            rows, targets, entries = self._prompt_rows(asks, n_tok)
         batch = []
         for s in seq_slots:
             td = self.state_slot[s]
@@ -587,7 +709,27 @@ class Worker:
             t.prefill_tokens = t.prefill_tokens[n_tok - 1:]
             td["next_input_token"] = t.prefill_tokens.pop(0)
             batch.append(chunk)
-        self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots))   # logits discarded (:776)
+        if not asks:
+            self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots))   # logits discarded (:776)
+            return None
+        # prompt logprobs: the head output of every row of the asking sequences, a block at a time, straight into the logprob
+        # kernel (the target of row (b, t) is the prompt token after it); the results reach the host behind an event like the ids
+        rows_dev, targets_dev = self._upload_int32(rows, targets)
+        lp = torch.empty((len(rows), k + 1), dtype=torch.float32, device=self.device)
+        ids = torch.empty((len(rows), k), dtype=torch.int32, device=self.device)
+
+        def sink(r0, block):
+            v, i = ops.token_logprobs(block, k, targets=targets_dev[r0:r0 + block.shape[0]])
+            lp[r0:r0 + block.shape[0]].copy_(v)
+            ids[r0:r0 + block.shape[0]].copy_(i)
+
+        self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots), logit_rows=rows_dev, row_sink=sink)
+        event = None
+        plp = self._download_plp(entries, lp, ids)
+        if self.device.type == "cuda":
+            event = torch.cuda.Event()
+            event.record()
+        return {"rows": [], "ids": None, "event": event, "raw": {}, "status": False, "plp": plp}
 
     # ------------------------------------------------------------------ main loop
     def step(self) -> bool:
@@ -641,8 +783,10 @@ class Worker:
         else:
             self.seq_forward_count_down = 0
         if seq and (self.seq_forward_count_down < 1 or (self.prefill_when_underfilled and 2 * len(dec) < self.max_batch_size)):
-            self._run_forward_seq(seq)
+            rec_seq = self._run_forward_seq(seq)
             self.seq_forward_count_down = max(1, self.decode_prefill_ratio)
+            if rec_seq is not None:                         # (prompt logprobs of the chunk: handled with this step's other results)
+                rec = [rec, rec_seq] if rec is not None else rec_seq
         if self.run_ahead:
             rec, self._inflight = self._inflight, rec
         self._handle_results(rec)
