@@ -106,6 +106,12 @@ class Task:
     # "top_logprobs"}) messages in position order before the first token; position 0 is None.  With max_tokens=0 the request only
     # scores: it ends (length) once the last position is known, without feeding the last prompt token or sampling anything
     prompt_logprobs: Optional[int] = None
+    # parallel choices (n) of one prompt: the group's first task (choice 0) carries the others (choices 1..n-1, each with its own
+    # queues, tables and finish) in `siblings`; the worker admits the group into n slots at once, prefills the prompt once and copies
+    # the state into the siblings' slots before the last prompt token (DESIGN.md "Parallel choices (n)").  A seeded choice j draws
+    # from Philox stream j, so choice 0 reproduces the single request with the same seed
+    choice_index: int = 0
+    siblings: List["Task"] = field(default_factory=list)
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -137,6 +143,22 @@ class Task:
                 raise ValueError(f"logit_bias: the bias of token {t} is not a finite number")
             checked[t] = float(v)
         self.logit_bias = checked
+        self.check_group()
+
+    def check_group(self) -> None:
+        """Validates choice_index and siblings (at construction, and by whoever assembles a group afterwards)."""
+        self.choice_index = _integer(self.choice_index, "choice_index")
+        self.siblings = list(self.siblings or [])
+        if self.choice_index < 0 or (self.siblings and self.choice_index != 0):
+            raise ValueError("choice_index must be >= 0, and 0 for the task that carries the siblings")
+        for j, sib in enumerate(self.siblings, start=1):
+            if not isinstance(sib, Task) or sib.siblings or sib.choice_index != j:
+                raise ValueError(f"sibling {j} must be a Task with choice_index {j} and no siblings of its own")
+        if self.siblings:
+            if any(t.prompt_logprobs is not None for t in [self] + self.siblings):
+                raise ValueError("parallel choices (n > 1) cannot be combined with prompt_logprobs")
+            if any(t.max_tokens == 0 for t in [self] + self.siblings):
+                raise ValueError("parallel choices (n > 1) need max_tokens > 0")
 
     def is_finished(self) -> bool:
         return RequestStatus.is_finished(self.request_status)

@@ -670,3 +670,67 @@ extern "C" int rwkv7_copy_slot_rows(int B, int C, const int32_t *slot_idx, const
                        static_cast<const f16 *>(src), static_cast<f16 *>(dst));
     return (int)hipGetLastError();
 }
+
+// Parallel choices of one prompt (Task.siblings): the state a prefill left in its slot, copied bit for bit into the sibling slots
+// of the group -- shift rows, WKV rows and the step counter.  Every group that forks in a worker step goes into ONE launch, grid
+// (pieces of a layer, L, groups): a workgroup loads kForkVec 16-byte vectors per lane of its piece of one source layer (the WKV
+// rows first, then the two shift rows) and stores them to every destination of its group, so the source is read once.  The
+// vectors are integer ones: a copy of bits (NaN payloads and -0 survive).  Lanes 0.. of workgroup (0, 0, g) copy the counter.
+namespace {
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kForkThreads = 256, kForkVec = 4;
+
+__device__ __forceinline__ u32x4 *fork_vec(u32x4 *shift, u32x4 *wkv, const int l, const int S, const int C, const int slot,
+                                           const int u) {
+    const int W = C * 8;                               // 16-byte vectors of a slot's WKV rows in one layer (H x 64 x 64 x 2 B)
+    if (u < W) return wkv + ((int64_t)l * S + slot) * W + u;
+    const int R = C >> 3, v = u - W, r = v >= R;       // then shift row r (0: time mix, 1: channel mix) of the layer
+    return shift + (((int64_t)l * 2 + r) * S + slot) * R + (v - r * R);
+}
+
+__global__ __launch_bounds__(kForkThreads) void fork_states_kernel(const int S, const int C, const int32_t *__restrict__ src,
+                                                                   const int32_t *__restrict__ dst_offs, const int32_t *__restrict__ dst,
+                                                                   u32x4 *__restrict__ shift, u32x4 *__restrict__ wkv,
+                                                                   int32_t *__restrict__ elapsed) {
+    const int g = blockIdx.z, l = blockIdx.y;
+    const int s = src[g], d0 = dst_offs[g], d1 = dst_offs[g + 1];
+    if (s < 0 || s >= S) return;
+    if (blockIdx.x == 0 && l == 0)
+        for (int j = d0 + threadIdx.x; j < d1; j += kForkThreads) {
+            const int d = dst[j];
+            if (d >= 0 && d < S) elapsed[d] = elapsed[s];
+        }
+    const int total = C * 8 + (C >> 2);
+    const int base = blockIdx.x * (kForkThreads * kForkVec) + threadIdx.x;
+    u32x4 v[kForkVec];
+#pragma unroll
+    for (int k = 0; k < kForkVec; k++) {
+        const int u = base + k * kForkThreads;
+        if (u < total) v[k] = *fork_vec(shift, wkv, l, S, C, s, u);
+    }
+    for (int j = d0; j < d1; j++) {
+        const int d = dst[j];
+        if (d < 0 || d >= S) continue;
+#pragma unroll
+        for (int k = 0; k < kForkVec; k++) {
+            const int u = base + k * kForkThreads;
+            if (u < total) *fork_vec(shift, wkv, l, S, C, d, u) = v[k];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int rwkv7_fork_states(int n_groups, int L, int S, int C, int H, const int32_t *src, const int32_t *dst_offs, const int32_t *dst,
+                                 void *shift, void *wkv, int32_t *elapsed, void *stream) {
+    if (n_groups < 0) return CHIRRUP_E_SHAPE;
+    if (n_groups == 0) return 0;
+    if (n_groups > 65535 || L <= 0 || L > 65535 || S <= 0 || H <= 0 || C != H * 64 || C > (1 << 20)) return CHIRRUP_E_SHAPE;
+    if (!src || !dst_offs || !dst || !shift || !wkv || !elapsed) return CHIRRUP_E_NULL;
+    if (mis16(shift) || mis16(wkv) || (reinterpret_cast<uintptr_t>(elapsed) & 3)) return CHIRRUP_E_ALIGN;
+    const int per_wg = kForkThreads * kForkVec;
+    const unsigned pieces = (unsigned)((C * 8 + (C >> 2) + per_wg - 1) / per_wg);
+    hipLaunchKernelGGL(fork_states_kernel, dim3(pieces, (unsigned)L, (unsigned)n_groups), dim3(kForkThreads), 0,
+                       static_cast<hipStream_t>(stream), S, C, src, dst_offs, dst, static_cast<u32x4 *>(shift), static_cast<u32x4 *>(wkv),
+                       elapsed);
+    return (int)hipGetLastError();
+}

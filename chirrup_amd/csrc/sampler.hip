@@ -810,8 +810,8 @@ extern "C" int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits
 // ------------------------------------------------------------------------------------------------
 // Per-request seeded draws: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011) with the
 // standard multipliers and Weyl key increments.  A seeded request's uniform for its i-th sampled token is a pure function of
-// (seed, i): key = (lo32(seed), hi32(seed)), counter = (i, 0, 0, 0), u = (x0 >> 8) * 2^-24 -- exact in binary32, in
-// [0, 1 - 2^-24].  The counter lives in a per-slot table that the draw advances, so the draw does not depend on the slot, the
+// (seed, i): key = (lo32(seed), hi32(seed)), counter = (i, j, 0, 0) for choice j of the request (seeded = 1 + j; j = 0 for a single
+// choice), u = (x0 >> 8) * 2^-24 -- exact in binary32, in [0, 1 - 2^-24].  The counter lives in a per-slot table that the draw advances, so the draw does not depend on the slot, the
 // batch, the step or on graph / eager mode.
 namespace {
 
@@ -841,7 +841,7 @@ __global__ __launch_bounds__(256) void seeded_uniform_kernel(const int n, const 
     if (!seeded[s]) return;                                  // unseeded rows keep the caller's uniform
     const uint64_t seed = seeds[s];
     const uint32_t ctr = counters[s];
-    const uint32_t x0 = philox_x0(ctr, 0u, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t x0 = philox_x0(ctr, (uint32_t)(seeded[s] - 1), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));   // word 1: the choice
     uniform[i] = (float)(x0 >> 8) * 0x1p-24f;
     counters[s] = ctr + 1u;
 }

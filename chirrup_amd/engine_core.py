@@ -85,6 +85,7 @@ class AsyncEngineCore:
         self.is_initialized = False
         self.is_shutdown = False
         self.vocab_size = None                        # model_config.vocab_size, set by init(): completion() checks logit_bias ids
+        self.max_choices = None                       # a worker's slot count (batch_size - 1), set by init(): the largest n of completions()
         self.tokenizer = tokenizer
         self._worker_factory = worker_factory
 
@@ -167,6 +168,7 @@ class AsyncEngineCore:
             asyncio.set_event_loop(self.event_loop)
         self.worker_event_queue = ThreadSafeAsyncQueue(self.event_loop, asyncio.Queue(maxsize=worker_num * 100))
         self.vocab_size = int(model_config.vocab_size)
+        self.max_choices = int(batch_size) - 1
         self.is_initialized = True
         if self.tokenizer is None:
             from .tokenizer import TRIE_TOKENIZER
@@ -244,6 +246,40 @@ class AsyncEngineCore:
                                      return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
                                      logit_bias=logit_bias, prompt_logprobs=prompt_logprobs)
 
+    def completions(self, prompt_str: str, prefill_tokens: Optional[List[int]] = None, n: int = 1, **kw) -> List[AsyncEngineCompletion]:
+        """n parallel choices of one prompt: completion()'s keywords, one AsyncEngineCompletion per choice (index order).  Starting
+        any of them submits the group once; the worker prefills the prompt once and forks the state into n slots (DESIGN.md
+        "Parallel choices (n)").  Each choice is iterated and aborted on its own; a seeded choice j draws from Philox stream j, so
+        choice 0 equals completion() with the same seed.  1 <= n <= a worker's slot count; n > 1 excludes prompt_logprobs and
+        max_tokens=0 (ValueError).  n = 1 is completion()."""
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= (self.max_choices if self.max_choices is not None else n):
+            raise ValueError(f"n must be an integer in [1, {self.max_choices}] (a worker's slot count), got {n!r}")
+        if n == 1:
+            return [self.completion(prompt_str, prefill_tokens=prefill_tokens, **kw)]
+        if kw.get("prompt_logprobs") is not None:
+            raise ValueError("n > 1 cannot be combined with prompt_logprobs")
+        if kw.get("max_tokens", DEFAULT_SAMPLING_CONFIG["max_tokens"]) == 0:
+            raise ValueError("n > 1 needs max_tokens > 0")
+        if not prefill_tokens:
+            prefill_tokens = self.tokenizer.encode(prompt_str)
+        task_id = kw.pop("task_id", None) or str(uuid.uuid4())
+        choices = [self.completion(prompt_str, prefill_tokens=list(prefill_tokens), task_id=task_id if j == 0 else f"{task_id}:{j}",
+                                   **(kw if j == 0 else dict(kw, state=None)))       # (a cached prefix state is installed for choice 0)
+                   for j in range(n)]
+        submitted = []
+
+        def start_group():
+            if not submitted:
+                submitted.append(True)
+                self.task_queue.put_nowait(choices[0].task)      # the siblings ride with choice 0
+
+        for j, c in enumerate(choices):
+            c.task.choice_index = j
+            c.group_start = start_group
+        choices[0].task.siblings = [c.task for c in choices[1:]]
+        choices[0].task.check_group()
+        return choices
+
     def _on_worker_fatal(self, worker, exc) -> None:
         """Called on a dying worker's thread.  When it was the last live worker, nobody will ever pick up the
         requests still in the shared queue: complete them as aborted instead of leaving their clients waiting."""
@@ -257,8 +293,9 @@ class AsyncEngineCore:
                 task = self.task_queue.get_nowait()
             except Exception:                    # noqa: BLE001 -- queue.Empty
                 break
-            task.request_status = RequestStatus.FINISHED_ABORTED
-            task.output_queue.put_nowait(("task_completed", task))
+            for t in [task] + task.siblings:
+                t.request_status = RequestStatus.FINISHED_ABORTED
+                t.output_queue.put_nowait(("task_completed", t))
 
     def shutdown(self) -> None:
         if self.is_shutdown:

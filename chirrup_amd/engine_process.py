@@ -32,12 +32,15 @@ from .remote_arena import WIRE_KEY, PeerArenas, RemoteStateRef, is_wire_row
 _TASK_FIELDS = ("prompt_str", "prefill_tokens", "state", "task_id", "priority", "temperature", "top_p", "top_k", "presence_penalty",
                 "frequency_penalty", "penalty_decay", "max_tokens", "stop_tokens", "forbidden_tokens", "cache_prefill",
                 "cache_prefill_padding", "return_logits", "logprobs", "top_logprobs", "seed", "logit_bias",
-                "prompt_logprobs")
+                "prompt_logprobs", "choice_index")
 _RESULT_FIELDS = ("request_status", "generated_tokens", "decoded_texts", "prefill_tokens")
 
 
 def task_to_wire(task: Task) -> Dict[str, Any]:
+    """The task as a picklable dict; a group of parallel choices is ONE item: the siblings travel inside choice 0's dict."""
     d = {k: getattr(task, k) for k in _TASK_FIELDS}
+    if task.siblings:
+        d["siblings"] = [dict({k: getattr(t, k) for k in _TASK_FIELDS}, state=None) for t in task.siblings]
     if isinstance(d["state"], RemoteStateRef):                           # a row of a worker's arena: its address travels, the
         d["state"] = d["state"].wire()                                   # handle stays pinned in the router until it is installed
         return d
@@ -184,6 +187,11 @@ class RemoteTaskQueue:
 
     def get_nowait(self) -> Task:
         d = self._pull()                                # queue.Empty when there is nothing to pull
+        siblings = [self._local_task(sd) for sd in d.pop("siblings", None) or ()]     # parallel choices: the whole group lands here
+        return self._local_task(d, siblings)
+
+    def _local_task(self, d: Dict[str, Any], siblings=()) -> Task:
+        """The worker-side Task of a wire dict: its own result sink and abort queue, its acceptance reported to the router."""
         ev = queue.Queue()
         with self._lock:
             self.local_events[d["task_id"]] = ev
@@ -193,9 +201,10 @@ class RemoteTaskQueue:
             if self._early_aborts.pop(d["task_id"], 0) is None:
                 ev.put_nowait(("abort", None))
         self._result_q.put((d["task_id"], ("__accepted__", self._wid)))
+        extra = {"siblings": list(siblings)} if siblings else {}
         return Task(output_queue=ResultSink(self._result_q, d["task_id"], on_done=self.forget, worker_id=self._wid, arena=self.arena,
                                             exports=self.exports),
-                    task_event_queue=ev, **d)
+                    task_event_queue=ev, **d, **extra)
 
     def deliver_abort(self, task_id: str) -> None:
         with self._lock:
@@ -300,12 +309,14 @@ class ProcessTaskQueue:
         self._q, self._router, self._affinity, self.prefix_affinity = task_q, router, dict(affinity_qs or {}), prefix_affinity
 
     def put_nowait(self, task: Task):
-        self._router.register(task)
+        for t in [task] + task.siblings:                # (parallel choices: every choice has its own channel)
+            self._router.register(t)
         if isinstance(task.state, RemoteStateRef) and task.state.arena.is_dead(task.state.worker_id):
             # the row's worker ended after the hit was handed out: the state no longer exists, and the request carries only the
             # tokens BEHIND the cached prefix -- it cannot be prefilled again here.  Completed as aborted; the client retries
             # (its next cache lookup misses: RemoteArena.ref returns None for a dead worker's rows).
-            self._router.finish_aborted(task)
+            for t in [task] + task.siblings:
+                self._router.finish_aborted(t)
             return
         wire = task_to_wire(task)
         if isinstance(task.state, RemoteStateRef):
@@ -327,7 +338,8 @@ class ProcessTaskQueue:
         q_, out = self._affinity.get(worker_id), []
         while q_ is not None:
             try:
-                out.append(q_.get_nowait()["task_id"])
+                d = q_.get_nowait()
+                out.extend([d["task_id"]] + [sd["task_id"] for sd in d.get("siblings", ())])
             except queue.Empty:
                 break
             except Exception:                           # noqa: BLE001 -- a queue whose peer died mid-write

@@ -36,11 +36,17 @@ class AsyncEngineCompletion:
                          return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
                          logit_bias=dict(logit_bias or {}), prompt_logprobs=prompt_logprobs)
         self._task_queue = task_queue
+        # one choice of a request with parallel choices (AsyncEngineCore.completions): the callable that submits the whole group --
+        # once, whichever of its choices starts first
+        self.group_start = None
         self._submitted = False
         self.is_finished = False
 
     def start(self):
         self._submitted = True
+        if self.group_start is not None:
+            self.group_start()
+            return
         self._task_queue.put_nowait(self.task)
 
     def __aiter__(self):

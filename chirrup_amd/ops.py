@@ -616,6 +616,56 @@ def commit_sampled(ids, slot_idx, last_ids, occurrence, penalty_weight, alpha_pr
     _lib.check(rc, "rwkv7_commit_sampled")
 
 
+def _fork_groups(groups, S: int):
+    """groups [(src, [dst, ...])] -> (srcs, dst_offs, dsts) after the host checks of fork_states."""
+    srcs, offs, dsts = [], [0], []
+    for src, ds in groups:
+        srcs.append(int(src))
+        dsts.extend(int(d) for d in ds)
+        offs.append(len(dsts))
+    bad = [x for x in srcs + dsts if not 0 <= x < S]
+    if bad:
+        raise _lib.ChirrupAmdError(f"fork_states: slot {bad[0]} is outside [0, {S})")
+    if len(set(dsts)) != len(dsts):
+        raise _lib.ChirrupAmdError("fork_states: a destination slot appears twice")
+    if set(dsts) & set(srcs):
+        raise _lib.ChirrupAmdError("fork_states: a destination slot is the source of a group")
+    return srcs, offs, dsts
+
+
+def fork_states(pool, groups) -> None:
+    """Parallel choices: copies the state of slot `src` into every slot of `dsts`, bit for bit, for each (src, dsts) of `groups`, in
+    ONE launch (include/chirrup_amd.h: rwkv7_fork_states).  pool = [shift [L, 2, S, C], wkv [L, S, H, 64, 64], elapsed [S]] -- the
+    worker's state tables.  Destinations must be distinct, in range and no group's source (checked here).  CPU tensors (any dtype:
+    fake backends) take torch copies; GPU tensors always take the kernel (binary16 tables, int32 elapsed)."""
+    shift, wkv, elapsed = pool
+    S = elapsed.shape[0]
+    srcs, offs, dsts = _fork_groups(groups, S)
+    if not dsts:
+        return
+    if shift.dim() != 4 or shift.shape[1] != 2 or shift.shape[2] != S or wkv.dim() < 2 or wkv.shape[1] != S or wkv.shape[0] != shift.shape[0]:
+        raise _lib.ChirrupAmdError("fork_states: expected shift [L, 2, S, C], wkv [L, S, ...], elapsed [S]")
+    if not elapsed.is_cuda:
+        for g, src in enumerate(srcs):
+            d = torch.tensor(dsts[offs[g]:offs[g + 1]], dtype=torch.long)
+            if d.numel() == 0:
+                continue
+            s = torch.full_like(d, src)
+            for t, dim in ((shift, 2), (wkv, 1), (elapsed, 0)):
+                t.index_copy_(dim, d, t.index_select(dim, s))
+        return
+    L, _, _, C = shift.shape
+    _chk(shift, "shift", torch.float16)
+    _chk(wkv, "wkv", torch.float16, (L, S, C // HEAD_SIZE, HEAD_SIZE, HEAD_SIZE))
+    _chk(elapsed, "elapsed", torch.int32, (S,))
+    host = torch.tensor(srcs + offs + dsts, dtype=torch.int32).pin_memory()     # one non-blocking copy: no host synchronisation
+    dev = host.to(elapsed.device, non_blocking=True)
+    n = len(srcs)
+    rc = _lib.load().rwkv7_fork_states(n, L, S, C, C // HEAD_SIZE, _ptr(dev), _ptr(dev[n:]), _ptr(dev[2 * n + 1:]), _ptr(shift), _ptr(wkv),
+                                       _ptr(elapsed), _stream())
+    _lib.check(rc, "rwkv7_fork_states")
+
+
 class TiledWeight:
     """A [N, K] fp16 weight re-laid as 16-KiB tile images for the ring GEMM (include/chirrup_amd.h:
     skinny_tile_weight).  Accepted wherever the skinny_* wrappers take a weight."""
@@ -1189,22 +1239,22 @@ def seed_int64(seed: int) -> int:
     return b - (1 << 64) if b >> 63 else b
 
 
-def philox_uniform(seed: int, i):
-    """The uniform of a seeded request's draw(s) i (int or array): (x0 >> 8) * 2^-24 of Philox(counter (i, 0, 0, 0),
-    key (lo32(seed), hi32(seed))), as binary32."""
+def philox_uniform(seed: int, i, stream: int = 0):
+    """The uniform of a seeded request's draw(s) i (int or array): (x0 >> 8) * 2^-24 of Philox(counter (i, stream, 0, 0),
+    key (lo32(seed), hi32(seed))), as binary32.  stream: the choice index j of a request with parallel choices (0: a single one)."""
     import numpy as np
 
     s = seed_bits(seed)
     i = np.asarray(i, np.uint64)
-    ctr = np.stack([i, np.zeros_like(i), np.zeros_like(i), np.zeros_like(i)], axis=-1)
+    ctr = np.stack([i, np.full_like(i, int(stream) & 0xFFFFFFFF), np.zeros_like(i), np.zeros_like(i)], axis=-1)
     x0 = philox4x32_10(ctr, np.array([s & 0xFFFFFFFF, s >> 32], np.uint64))[..., 0]
     return ((x0 >> np.uint32(8)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
 
 
 def seeded_uniform(rows, slot_idx, seeds, seeded, counters, uniform) -> None:
     """Overwrites the uniforms of the seeded rows with their Philox draws (include/chirrup_amd.h: rwkv7_seeded_uniform): for row
-    list entry i, slot s = slot_idx[rows[i]]; when seeded[s], uniform[i] = philox_uniform(seeds[s], counters[s]) and counters[s]
-    += 1.  rows int32 [n]; slot_idx int32; seeds int64 (the uint64 bits), seeded int32, counters int32 (uint32 bits) per slot;
+    list entry i, slot s = slot_idx[rows[i]]; when seeded[s] (1 + the choice's stream), uniform[i] = philox_uniform(seeds[s],
+    counters[s], seeded[s] - 1) and counters[s] += 1.  rows int32 [n]; slot_idx int32; seeds int64 (the uint64 bits), seeded int32, counters int32 (uint32 bits) per slot;
     uniform fp32 [n].  CPU tensors take the numpy form (fake backends); GPU tensors always take the kernel."""
     n = rows.numel()
     if uniform.dtype != torch.float32 or uniform.numel() != n:
@@ -1231,7 +1281,7 @@ def _seeded_uniform_host(rows, slot_idx, seeds, seeded, counters, uniform):
         s = sl[r]
         if int(seeded[s]):
             c = int(counters[s]) & 0xFFFFFFFF
-            uniform[i] = float(philox_uniform(int(seeds[s]), c))
+            uniform[i] = float(philox_uniform(int(seeds[s]), c, int(seeded[s]) - 1))
             counters[s] = (c + 1) - (1 << 32) if c + 1 >= (1 << 31) else c + 1     # uint32 bits in an int32 table
 
 

@@ -70,6 +70,9 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     # (a decimal string) -> a bias in [-100, 100] added to that token's logit
     seed: Optional[int] = Field(None, ge=-(1 << 63), lt=1 << 64)
     logit_bias: Optional[Dict[str, float]] = None
+    # n choices of the prompt (prefilled once; at most a worker's slot count, else 400): choices[j] with index j, a seeded choice j
+    # draws from its own Philox stream (choice 0 equals the n = 1 request with the same seed)
+    n: int = Field(1, ge=1, le=128)
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):
@@ -249,6 +252,9 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         vocab = getattr(engine, "vocab_size", None)
         if vocab is not None and bias and max(bias) >= vocab:
             raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        n = request.n
+        if n > 1 and n > (getattr(engine, "max_choices", None) or 1):
+            raise HTTPException(status_code=400, detail=f"n = {n} exceeds the {getattr(engine, 'max_choices', None) or 1} choices a worker holds")
         try:
             prompt, pad = chat_prompt(request.messages, request.model)
             tokens = ([0] if request.pad_zero else []) + engine.tokenizer.encode(prompt)
@@ -258,55 +264,64 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
             rest, state, n_cached = tokens, None, 0
             if request.use_state_cache and state_cache is not None:
                 rest, state, n_cached = await state_cache.check_and_wait_prefill(tokens, pad)
-            completion = engine.completion(prompt_str=prompt, prefill_tokens=rest, state=state, temperature=request.temperature,
-                                           top_p=request.top_p, max_tokens=request.max_tokens, presence_penalty=request.presence_penalty,
-                                           frequency_penalty=request.frequency_penalty, penalty_decay=request.penalty_decay,
-                                           stop_tokens=set(DEFAULT_STOP_TOKENS + stops),
-                                           cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
-                                           **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}),
-                                           **({"seed": request.seed} if request.seed is not None else {}),
-                                           **({"logit_bias": bias} if bias else {}))
+            kw = dict(prompt_str=prompt, prefill_tokens=rest, state=state, temperature=request.temperature,
+                      top_p=request.top_p, max_tokens=request.max_tokens, presence_penalty=request.presence_penalty,
+                      frequency_penalty=request.frequency_penalty, penalty_decay=request.penalty_decay,
+                      stop_tokens=set(DEFAULT_STOP_TOKENS + stops),
+                      cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
+                      **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}),
+                      **({"seed": request.seed} if request.seed is not None else {}),
+                      **({"logit_bias": bias} if bias else {}))
+            choices = engine.completions(n=n, **kw) if n > 1 else [engine.completion(**kw)]      # one prefill for the n choices
         except HTTPException:
             raise
         except Exception as e:                                  # noqa: BLE001 -- app.py:231
             raise HTTPException(status_code=500, detail=f"generation failed: {e}")
-        splitter = ThinkSplitter()
-        splitter.feed(prompt.split("\n\n")[-1])                 # the assistant cue sets the splitter's starting part (app.py:243)
+        splitters = [ThinkSplitter() for _ in choices]
+        for splitter in splitters:
+            splitter.feed(prompt.split("\n\n")[-1])             # the assistant cue sets the splitter's starting part (app.py:243)
         cid, created_at = f"chatcmpl-{uuid.uuid4().hex}", int(time.time())
 
-        def chunk(delta: Dict[str, Any], finish=None, logprobs=None) -> str:
+        def chunk(delta: Dict[str, Any], finish=None, logprobs=None, index: int = 0) -> str:
             body = {"id": cid, "object": "chat.completion.chunk", "created": created_at, "model": request.model,
-                    "choices": [{"index": 0, "delta": delta, "finish_reason": finish}]}
+                    "choices": [{"index": index, "delta": delta, "finish_reason": finish}]}
             if logprobs:
                 body["choices"][0]["logprobs"] = {"content": logprobs}
             return f"data: {json.dumps(body, ensure_ascii=False)}\n\n"
 
+        async def one(index: int, completion, splitter, q: asyncio.Queue):
+            """One choice: streamed chunks with its index and its own finish chunk, or (choice object, completion tokens)."""
+            content, reasoning, lps, pending = [], [], [], []
+            async for st, piece in events_of(completion, splitter, tokens[:n_cached]):
+                if st == "logprobs":                           # rides on the next chunk sent (a token may send none)
+                    lps.append(piece)
+                    pending.append(piece)
+                    continue
+                (content if st == "content" else reasoning).append(piece)
+                if request.stream:
+                    q.put_nowait(chunk({"content": piece} if st == "content" else {"content": "", "reasoning_content": piece},
+                                       logprobs=pending, index=index))
+                    pending = []
+            if request.stream:
+                if pending:
+                    q.put_nowait(chunk({"content": ""}, logprobs=pending, index=index))
+                q.put_nowait(chunk({}, "stop", index=index))
+                return None
+            choice = {"index": index, "finish_reason": "stop",
+                      "message": {"role": "assistant", "content": "".join(content), "reasoning_content": "".join(reasoning)}}
+            if request.logprobs:
+                choice["logprobs"] = {"content": lps}
+            return choice, len(completion.task.generated_tokens)
+
         async def produce(q: asyncio.Queue):
             try:
-                content, reasoning, lps, pending = [], [], [], []
-                async for st, piece in events_of(completion, splitter, tokens[:n_cached]):
-                    if st == "logprobs":                       # rides on the next chunk sent (a token may send none)
-                        lps.append(piece)
-                        pending.append(piece)
-                        continue
-                    (content if st == "content" else reasoning).append(piece)
-                    if request.stream:
-                        q.put_nowait(chunk({"content": piece} if st == "content" else {"content": "", "reasoning_content": piece},
-                                           logprobs=pending))
-                        pending = []
+                results = await asyncio.gather(*[one(j, c, s, q) for j, (c, s) in enumerate(zip(choices, splitters))])
                 if request.stream:
-                    if pending:
-                        q.put_nowait(chunk({"content": ""}, logprobs=pending))
-                    q.put_nowait(chunk({}, "stop"))
-                    q.put_nowait("data: [DONE]\n\n")
+                    q.put_nowait("data: [DONE]\n\n")             # once every choice has ended
                 else:
-                    n_out = len(completion.task.generated_tokens)
-                    choice = {"index": 0, "finish_reason": "stop",
-                              "message": {"role": "assistant", "content": "".join(content), "reasoning_content": "".join(reasoning)}}
-                    if request.logprobs:
-                        choice["logprobs"] = {"content": lps}
+                    n_out = sum(r[1] for r in results)
                     q.put_nowait(json.dumps({"id": cid, "object": "chat.completion", "created": created_at, "model": request.model,
-                                             "choices": [choice],
+                                             "choices": [r[0] for r in results],
                                              "usage": {"prompt_tokens": len(tokens), "completion_tokens": n_out,
                                                        "total_tokens": len(tokens) + n_out}}, ensure_ascii=False))
             except Exception as e:                              # noqa: BLE001 -- reported in-band like the reference (app.py:297-301)
@@ -328,9 +343,10 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                     if item is None:
                         return
                     yield item
-            finally:                                            # client gone or done: stop generating
+            finally:                                            # client gone or done: stop generating (every choice)
                 task.cancel()
-                completion.abort()
+                for c in choices:
+                    c.abort()
                 if state_cache is not None and request.use_state_cache and n_cached + pad != len(tokens):
                     # this request was the one prefilling its prefix: if it ended without exporting it (abort, failure), the requests
                     # parked on that prefix must not wait for ever (the reference leaves them waiting) -- they look again and prefill

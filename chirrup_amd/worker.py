@@ -76,10 +76,12 @@ def min_swaps_to_target_fast(lst, elements):
 
 def _empty_slot() -> dict:
     # feedback: the slot's next decode input is last_ids[slot] on the device.  Prompt logprobs (task.prompt_logprobs set):
-    # plp_prompt = the tokens as admitted, plp_next = index of the next one to feed, plp_sent = positions already sent
+    # plp_prompt = the tokens as admitted, plp_next = index of the next one to feed, plp_sent = positions already sent.
+    # Parallel choices: siblings = [(slot, task)] of the choices waiting suspended for this slot's prefill (until the fork); orphan:
+    # choice 0 has aborted and the slot prefills on for its live siblings only
     return {"task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
             "state_category": StateCategory.EMPTY, "prefilled_tokens": [], "prefill_cached": False,
-            "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0}
+            "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0, "siblings": None, "orphan": False}
 
 
 class Worker:
@@ -126,6 +128,8 @@ class Worker:
         self.shutdown_flag = False
         self.loop_time_recorder = deque(maxlen=10)
         self.iterations = 0
+        self._held = None                             # a group of parallel choices pulled before n slots were free
+        self._groups: List[Tuple[int, Task]] = []     # (slot, choice-0 task) of the admitted groups that have not forked yet
 
     # ------------------------------------------------------------------ set-up
     def _load_model(self):
@@ -440,11 +444,104 @@ class Worker:
                 prefills += td["state_category"] == StateCategory.FORWARD_SEQ
                 continue
             prefills += 1
+            task = self._next_task()
+            if task is None:
+                break
+            if task.siblings:
+                if not self._admit_group(task, slot):
+                    break
+                continue
+            self._install(task, slot)
+
+    def _next_task(self) -> Optional[Task]:
+        """The held group (nothing behind it is admitted first: FIFO), else the next task of the queue; None when there is none.  A
+        group of more choices than this worker has slots can never fit (the engine refuses such groups): it ends, aborted."""
+        if self._held is not None:
+            task, self._held = self._held, None
+            return task
+        while True:
             try:
                 task: Task = self.task_queue.get_nowait()
             except queue.Empty:
-                break
-            self._install(task, slot)
+                return None
+            if 1 + len(task.siblings) <= self.max_batch_size:
+                return task
+            for t in [task] + task.siblings:
+                t.request_status = RequestStatus.FINISHED_ABORTED
+                t.output_queue.put_nowait(("task_completed", t))
+
+    def _admit_group(self, task: Task, slot: int) -> bool:
+        """Parallel choices: choice 0 into `slot` (every slot before it is taken), choices 1..n-1 into the next free slots, suspended
+        until the fork.  Only when n slots are free at once; otherwise the group is held (returns False).  One prefill."""
+        n = 1 + len(task.siblings)
+        free = [s for s in range(slot, self.max_batch_size) if self.state_slot[s]["state_category"] == StateCategory.EMPTY]
+        if len(free) < n:
+            self._held = task
+            return False
+        self._install(task, slot)
+        td = self.state_slot[slot]
+        if td["task"] is not task:                     # ended at admission (an unreachable prefix state): so do its siblings
+            for t in task.siblings:
+                t.request_status = RequestStatus.FINISHED_ABORTED
+                t.output_queue.put_nowait(("task_completed", t))
+            return True
+        td["siblings"] = list(zip(free[1:n], task.siblings))
+        for s, t in td["siblings"]:
+            sd = _empty_slot()
+            sd.update(task=t, is_prefilling=True, state_category=StateCategory.FORWARD_ONE_SUSPENDED)
+            self.state_slot[s] = sd
+        self._groups.append((slot, task))
+        return True
+
+    def _live_siblings(self, td) -> List[Tuple[int, Task]]:
+        return [(s, t) for s, t in td["siblings"] or ()
+                if self.state_slot[s]["task"] is t and not RequestStatus.is_finished(t.request_status)]
+
+    def _orphan_on_abort(self, td) -> bool:
+        """Choice 0 of a group that has not forked has aborted: when choices are still live its slot prefills on for them (orphan)
+        -- the choice itself ends now, and the group's prefix state is not exported.  Returns True for an orphan."""
+        if td["orphan"]:
+            return True
+        if not self._live_siblings(td):
+            return False
+        t: Task = td["task"]
+        t.request_status = RequestStatus.FINISHED_ABORTED
+        t.output_queue.put_nowait(("task_completed", t))
+        td["orphan"] = td["prefill_cached"] = True
+        return True
+
+    def _run_forks(self):
+        """Groups whose choice-0 slot turned FORWARD_ONE_DECODE in this step (its state holds every prompt token but the last): ONE
+        ops.fork_states launch copies each state into the live siblings' slots, behind the forward that produced it and before the
+        forward that reads them (stream order, no host synchronisation).  Then the siblings' tables, and every live choice feeds
+        the last prompt token as its first decode row.  An orphan's slot is freed; a group whose choices all ended is dropped."""
+        forks, keep = [], []
+        for p, task in self._groups:
+            td = self.state_slot[p]
+            if td["task"] is not task:
+                continue
+            live = self._live_siblings(td)
+            if td["orphan"] and not live:              # every choice has aborted: the prefill stops
+                self.state_slot[p] = _empty_slot()
+                continue
+            if td["state_category"] != StateCategory.FORWARD_ONE_DECODE:
+                keep.append((p, task))
+                continue
+            td["siblings"] = None
+            forks.append((p, td, live))
+        self._groups = keep
+        if not any(live for _, _, live in forks):
+            return
+        assert all(s < self.real_state_size - 1 for _, _, live in forks for s, _ in live)      # never the parking slot
+        ops.fork_states(self.batch_state, [(p, [s for s, _ in live]) for p, _, live in forks if live])
+        for p, td, live in forks:
+            for s, t in live:
+                self._write_request_tables(t, s)
+                t.prefill_tokens = []
+                self.state_slot[s].update(state_category=StateCategory.FORWARD_ONE_DECODE, is_prefilling=False,
+                                          next_input_token=td["next_input_token"], prefilled_tokens=list(td["prefilled_tokens"]))
+            if td["orphan"]:
+                self.state_slot[p] = _empty_slot()
 
     def _install(self, task: Task, slot: int):
         s0, s1, s2 = self.batch_state
@@ -483,31 +580,7 @@ class Worker:
             s0[:, :, [slot], :] = task.state[0].to(s0.device, non_blocking=True)
             s1[:, [slot], :, :] = task.state[1].to(s1.device, non_blocking=True)
             s2[[slot]] = task.state[2].to(s2.device, non_blocking=True)
-        self.occurrence[slot].zero_()
-        self.alpha_presence_vector[slot].zero_()
-        if getattr(self, "_pen_lists", None) is not None:
-            self._pen_lists.reset(slot)
-        self.temperature_tensor[slot, 0] = task.temperature if task.temperature > 0 else 1.0
-        self.top_p_tensor[slot, 0] = task.top_p
-        self.top_k_tensor[slot, 0] = task.top_k
-        self.frequency_penalty_tensor[slot, 0] = task.frequency_penalty
-        self.penalty_decay_tensor[slot, 0] = task.penalty_decay
-        self.presence_penalty_tensor[slot, 0] = task.presence_penalty
-        self._greedy[slot] = is_greedy_row(task.temperature, task.top_p, task.top_k)
-        # stream-ordered writes: a run-ahead row of the slot's previous request still in flight reads (and advances) the old values
-        seeded = task.seed is not None
-        if seeded or self._seeded[slot]:
-            self.seeds[slot] = ops.seed_int64(task.seed) if seeded else 0
-            self.seeded[slot] = int(seeded)
-            self.counters[slot] = 0
-            self._seeded[slot] = seeded
-        n_bias = len(task.logit_bias)
-        if n_bias or self._bias_n[slot]:
-            if n_bias:
-                self.bias_ids[slot, :n_bias] = torch.tensor(list(task.logit_bias.keys()), dtype=torch.int32)
-                self.bias_values[slot, :n_bias] = torch.tensor(list(task.logit_bias.values()), dtype=torch.float32)
-            self.bias_counts[slot] = n_bias
-            self._bias_n[slot] = n_bias
+        self._write_request_tables(task, slot)
         plp_prompt = list(task.prefill_tokens) if task.prompt_logprobs is not None else None
         if plp_prompt is not None and len(plp_prompt) == 1:      # its one position has no logprob: sent at once
             task.output_queue.put_nowait(("prompt_logprobs", {"start": 0, "token_ids": list(plp_prompt), "logprobs": [None],
@@ -527,6 +600,34 @@ class Worker:
         td.update(task=task, is_prefilling=prefilling, next_input_token=first, state_category=cat, plp_prompt=plp_prompt,
                   plp_sent=1 if plp_prompt is not None and len(plp_prompt) == 1 else 0)
         self.state_slot[slot] = td
+
+    def _write_request_tables(self, task: Task, slot: int):
+        """The slot's penalty, sampling, seed and bias tables for `task` (at admission; a sibling choice's at the fork)."""
+        self.occurrence[slot].zero_()
+        self.alpha_presence_vector[slot].zero_()
+        if getattr(self, "_pen_lists", None) is not None:
+            self._pen_lists.reset(slot)
+        self.temperature_tensor[slot, 0] = task.temperature if task.temperature > 0 else 1.0
+        self.top_p_tensor[slot, 0] = task.top_p
+        self.top_k_tensor[slot, 0] = task.top_k
+        self.frequency_penalty_tensor[slot, 0] = task.frequency_penalty
+        self.penalty_decay_tensor[slot, 0] = task.penalty_decay
+        self.presence_penalty_tensor[slot, 0] = task.presence_penalty
+        self._greedy[slot] = is_greedy_row(task.temperature, task.top_p, task.top_k)
+        # stream-ordered writes: a run-ahead row of the slot's previous request still in flight reads (and advances) the old values
+        seeded = task.seed is not None
+        if seeded or self._seeded[slot]:
+            self.seeds[slot] = ops.seed_int64(task.seed) if seeded else 0
+            self.seeded[slot] = 1 + task.choice_index if seeded else 0     # Philox stream of the choice
+            self.counters[slot] = 0
+            self._seeded[slot] = seeded
+        n_bias = len(task.logit_bias)
+        if n_bias or self._bias_n[slot]:
+            if n_bias:
+                self.bias_ids[slot, :n_bias] = torch.tensor(list(task.logit_bias.keys()), dtype=torch.int32)
+                self.bias_values[slot, :n_bias] = torch.tensor(list(task.logit_bias.values()), dtype=torch.float32)
+            self.bias_counts[slot] = n_bias
+            self._bias_n[slot] = n_bias
 
     def _organize_batch(self):
         """Slot ids per category, in slot order (the reference returns contiguous ranges after
@@ -756,17 +857,19 @@ class Worker:
             assert cat != StateCategory.FINISHED
             if cat == StateCategory.EMPTY:
                 continue
-            if self._is_task_aborted(td):
+            if self._is_task_aborted(td) and not (td["siblings"] and self._orphan_on_abort(td)):
                 td["task"].request_status = RequestStatus.FINISHED_ABORTED
                 td["state_category"] = StateCategory.FINISHED
             elif cat == StateCategory.FORWARD_SEQ:
                 self._handle_forward_seq(td, slot)
             elif cat == StateCategory.FORWARD_ONE_PREFILL:
                 self._handle_forward_one_prefill_phase(td, slot)
-            if RequestStatus.is_finished(td["task"].request_status):
+            if RequestStatus.is_finished(td["task"].request_status) and not td["orphan"]:
                 done.append(slot)
         self._process_accomplished_tasks(done)
         self._fill_task_pool()
+        if self._groups:
+            self._run_forks()
         cats = self._organize_batch()
         dec, pre, seq = (cats[c] for c in (StateCategory.FORWARD_ONE_DECODE, StateCategory.FORWARD_ONE_PREFILL,
                                            StateCategory.FORWARD_SEQ))
@@ -828,8 +931,9 @@ class Worker:
             self._cleanup()
 
     def _fail_all_requests(self):
-        for td in list(getattr(self, "state_slot", {}).values()):
-            t = td.get("task")
+        held = getattr(self, "_held", None)
+        tasks = [td.get("task") for td in list(getattr(self, "state_slot", {}).values())] + ([held] + held.siblings if held else [])
+        for t in tasks:
             if t is not None and not RequestStatus.is_finished(t.request_status):
                 t.request_status = RequestStatus.FINISHED_ABORTED
                 try:

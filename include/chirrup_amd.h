@@ -466,6 +466,14 @@ int rwkv7_advance_elapsed(int B, int T, const int32_t *slot_idx, int32_t *elapse
 /* dst[slot_idx[b]][0..C) = src[slot_idx[b]][0..C) for b < B: binary16 tables [n_slots][C] (C % 8 == 0, slots distinct) -- the commit of
  * a chunk's token-shift carry into the slot table (the T > 1 form of rwkv7_add_ln_mix writes the carry to a side table). */
 int rwkv7_copy_slot_rows(int B, int C, const int32_t *slot_idx, const void *src, void *dst, void *stream);
+/* Parallel choices of one prompt: group g < n_groups copies slot src[g] of the worker's state tables to every slot
+ * dst[dst_offs[g] .. dst_offs[g + 1]), bit for bit -- shift binary16 [L][2][S][C], wkv binary16 [L][S][H][64][64] and elapsed int32
+ * [S].  ONE launch for all groups; a workgroup reads its piece of a source layer once and writes it to each destination of its group
+ * (16 B per lane, integer vectors: NaN payloads and -0 survive).  Destinations must be distinct, in [0, S) and no group's source
+ * (the caller checks; slots outside [0, S) are skipped).  C == H * 64; shift and wkv 16-byte aligned.  n_groups == 0 launches
+ * nothing.  Bytes per group: one slot's state read once, written once per destination. */
+int rwkv7_fork_states(int n_groups, int L, int S, int C, int H, const int32_t *src, const int32_t *dst_offs, const int32_t *dst,
+                      void *shift, void *wkv, int32_t *elapsed, void *stream);
 
 /*
  * Sort-free top-p / top-k / temperature sampling of n_rows rows of `logits` (binary16 [B][V], V <= 65536,
@@ -495,9 +503,10 @@ int rwkv7_token_logprobs(int n_rows, int V, int K, const void *logits, const int
 /*
  * Per-request seeded uniforms for the sampler (Philox4x32-10, M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9,
  * W1 = 0xBB67AE85).  For each i < n_rows: r = rows[i], s = slot_idx[r].  When seeded[s] != 0:
- * uniform[i] = (x0 >> 8) * 2^-24 with x0 the first word of Philox(counter = (counters[s], 0, 0, 0),
+ * uniform[i] = (x0 >> 8) * 2^-24 with x0 the first word of Philox(counter = (counters[s], seeded[s] - 1, 0, 0),
  * key = (lo32(seeds[s]), hi32(seeds[s]))), then counters[s] += 1.  Rows whose slot is not seeded keep uniform[i].
- * A slot appears at most once among the rows.  n_rows == 0 launches nothing; seeds must be 8-byte aligned.
+ * seeded[s] is 0 (unseeded) or 1 + j for choice j of a request with parallel choices (j = 0 for a single choice): counter word 1
+ * is the choice's stream.  A slot appears at most once among the rows.  n_rows == 0 launches nothing; seeds must be 8-byte aligned.
  */
 int rwkv7_seeded_uniform(int n_rows, const int32_t *rows, const int32_t *slot_idx, const uint64_t *seeds,
                          const int32_t *seeded, uint32_t *counters, float *uniform, void *stream);
