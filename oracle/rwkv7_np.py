@@ -132,24 +132,37 @@ def tmix(layer_id, H, x, x_prev, v_first, S, z, att, elapsed_t, att8=None, mm8_b
     w = linear(tanh_h(linear(xw, g("w1"))), g("w2"), bias=g("w0"))
     k = proj(xk, "key")
     v = proj(xv, "value")
-    a = sigmoid_h(linear(linear(xa, g("a1")), g("a2"), bias=g("a0")))
+    a_pre = linear(linear(xa, g("a1")), g("a2"), bias=g("a0"))
     gate = linear(sigmoid_h(linear(xg, g("g1"))), g("g2"))
+    vg_pre = None if layer_id == 0 else linear(linear(xv, g("v1")), g("v2"), bias=g("v0"))
+    xo, v = tmix_core(H, r, w, k, v, a_pre, vg_pre, v_first, gate, g("k_k"), g("k_a"), g("r_k"), g("ln_x.weight"), g("ln_x.bias"),
+                      S, elapsed_t)
+    if layer_id == 0:
+        v_first = v                                                       # :636
+    return proj(xo, "output"), v_first                                    # :649
+
+
+def tmix_core(H, r, w, k, v, a_pre, vg_pre, v_first, gate, k_k, k_a, r_k, lnx_w, lnx_b, S, elapsed_t, slot_idx=None, eps=64e-5):
+    """The core of the time mix between the projections and att.output, Albatross/rwkv7.py:629-649: what the fused kernel
+    rwkv7_tmix_wkv7_fused computes.  r, w, k, v, gate [B,T,C]; a_pre / vg_pre are the PRE-sigmoid gates (vg_pre None: layer 0,
+    no v gate); S [n_slots,H,64,64] is updated in place (rows slot_idx, or 0..B-1).  Returns (xo * gate, v after the gate)."""
+    B, T, C = r.shape
+    N = C // H
+    a = sigmoid_h(a_pre)
     # F.normalize(p=2, dim=-1): x / max(||x||, 1e-12) with the norm rounded to f16 first (:632)
-    kk_in = (k * g("k_k")).reshape(B, T, H, N)
+    kk_in = (k * k_k).reshape(B, T, H, N)
     nrm = np.sqrt((kk_in.astype(F32) ** 2).sum(axis=-1, keepdims=True, dtype=F32)).astype(F16)
     nrm = np.maximum(nrm, F16(1e-12))
     kk = (kk_in / nrm).reshape(B, T, C)
-    k = k * (F16(1.0) + (a - F16(1.0)) * g("k_a"))                      # :633
+    k = k * (F16(1.0) + (a - F16(1.0)) * k_a)                            # :633
     kka = kk * a                                                          # :634
-    if layer_id == 0:
-        v_first = v                                                       # :636
-    else:
-        v = v + (v_first - v) * sigmoid_h(linear(linear(xv, g("v1")), g("v2"), bias=g("v0")))  # :637
-    y = native.wkv7_seq(S, r, w, k, v, -kk, kka, elapsed_t)               # :645 (a = -kk, b = kk*a)
-    xo = group_norm_heads(y.reshape(B * T, C), H, g("ln_x.weight"), g("ln_x.bias")).reshape(B, T, C)   # :647
-    bonus = ((r * k * g("r_k")).reshape(B, T, H, N).astype(F32).sum(axis=-1, keepdims=True, dtype=F32)).astype(F16)
+    if vg_pre is not None:
+        v = v + (v_first - v) * sigmoid_h(vg_pre)                         # :637
+    y = native.wkv7_seq(S, r, w, k, v, -kk, kka, elapsed_t, slot_idx=slot_idx)   # :645 (a = -kk, b = kk*a)
+    xo = group_norm_heads(y.reshape(B * T, C), H, lnx_w, lnx_b, eps=eps).reshape(B, T, C)   # :647
+    bonus = ((r * k * r_k).reshape(B, T, H, N).astype(F32).sum(axis=-1, keepdims=True, dtype=F32)).astype(F16)
     xo = xo + (bonus * v.reshape(B, T, H, N)).reshape(B, T, C)            # :648
-    return proj(xo * gate, "output"), v_first                              # :649
+    return xo * gate, v
 
 
 def cmix(x, x_prev, x_k, K_, V_):

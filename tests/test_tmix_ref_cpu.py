@@ -1,0 +1,256 @@
+"""CPU tests of the interval reference of the fused time-mix core (tests/tmix_ref.py): what shows, without a GPU, that the GPU
+tests of tests/test_fused_gpu.py can fail and that they hide nothing.  Legitimate binary32 evaluation orders of the four
+reductions pass the checker on every case, defective evaluations are rejected, and the reference meets the conditions that keep
+it sharp (shares of single-pattern elements per case: DESIGN.md, "Exact where unambiguous")."""
+import numpy as np
+import pytest
+
+import tmix_ref as R
+from oracle import rwkv7_np as M
+from util import bits
+
+F16, F32 = np.float16, np.float32
+
+_CACHE = {}
+
+
+def case(name):
+    if name not in _CACHE:
+        _CACHE.clear()                                   # one case at a time: the large ones hold ~100 MB of state
+        inp, stats = R.case_inputs(name)
+        _CACHE[name] = (inp, stats, R.reference(inp))
+    return _CACHE[name]
+
+
+def oracle_path(inp):
+    """The existing binary32 oracle (oracle/rwkv7_np.tmix_core: numpy's pairwise sums)."""
+    S = np.ascontiguousarray(inp["state"]).copy()
+    with np.errstate(all="ignore"):
+        out, _ = M.tmix_core(inp["k"].shape[2] // 64, inp["r"], inp["w"], inp["k"], inp["v"], inp["a_pre"],
+                             None if inp["layer0"] else inp["vg_pre"], inp["v_first"], inp["g"], inp["k_k"], inp["k_a"], inp["r_k"],
+                             inp["lnx_w"], inp["lnx_b"], S, inp["et"], slot_idx=inp["slot_idx"], eps=inp["eps"])
+    return out, S
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_conditions_and_legitimate_orders(name):
+    """Per case, on the reference alone: no ambiguity left in the gating, the generator touched little, the intervals are
+    sharp, everything is finite.  Then three binary32 evaluations of the reductions (numpy pairwise = the oracle path, the xor
+    butterfly of wave_sum, sequential): state bit for bit, out inside the intervals."""
+    inp, st, ref = case(name)
+    regime = R.CASES[name]["regime"]
+    assert ref["amb_gate"] == 0 and ref["amb_norm"] == 0
+    assert st["replaced"] <= 0.01 * st["gates"] and st["redrawn"] <= 0.05 * st["heads"], st
+    print(f"{name}: replaced {st['replaced']}/{st['gates']} redrawn {st['redrawn']}/{st['heads']} single {ref['single']:.4f} "
+          f"wide {ref['wide']:.4f} widest {ref['widest']}")
+    assert ref["single"] >= (0.90 if regime == "plain" else 0.50), ref["single"]
+    assert ref["wide"] <= (0.03 if regime == "plain" else 0.10), ref["wide"]
+    assert np.isfinite(ref["state"].astype(F32)).all()
+    assert np.isfinite(ref["lo"].astype(F32)).all() and np.isfinite(ref["hi"].astype(F32)).all()
+    for order, (out, S) in (("oracle", oracle_path(inp)), ("butterfly", R.emulate(inp, "butterfly")),
+                            ("sequential", R.emulate(inp, "sequential"))):
+        assert np.array_equal(bits(S), bits(ref["state"])), order
+        R.assert_check(out, ref["lo"], ref["hi"], name=f"{name} {order}")
+    if regime == "offset":                                 # the regime keeps its power: E[y^2] - mean^2 is rejected
+        out, _ = R.emulate(inp, "butterfly", "one_pass_variance")
+        res = R.check(out, ref["lo"], ref["hi"])
+        print(f"{name}: one-pass variance rejected on {res['bad']} of {res['n']}")
+        assert res["bad"] >= 0.01 * res["n"]
+
+
+# The cases the mutants are run on (768 wide, 8 x 2 rows in 10 slots: 12 288 outputs, 491 520 state elements; the offset one
+# 3 x 1 rows in 6 slots: 2 304 outputs).
+MUT_CASES = {
+    "plain": dict(B=8, T=2, C=768, layer0=False, regime="plain", n_slots=10, seed=11),
+    "plain-layer0": dict(B=8, T=2, C=768, layer0=True, regime="plain", n_slots=10, seed=12),
+    "offset": dict(B=3, T=1, C=768, layer0=False, regime="offset", n_slots=6, seed=13),
+    "outlier": dict(B=8, T=2, C=768, layer0=False, regime="outlier", n_slots=10, seed=14),
+}
+# mutant -> (case, least number of out elements rejected, least number of state elements differing).  The minima are what the
+# defect must at least move, far below what it does move: a wrong eps scales every group norm by up to (V + 64e-5)/(V + 1e-5),
+# visible in binary16 where the head's variance is below ~1 (>= 100 of 12 288 here, every element in the offset regime whose
+# heads have a variance of ~0.01); a skipped rounding changes the next rounding in a fixed share of the elements; a swapped
+# parameter, a gate at layer 0 or a shifted dither touch (nearly) everything; half a wave is wrong in all of head 0 (16 rows x 64
+# outputs, 8 slots x 4096 state elements); swapped heads are two heads' 4096 elements each; the overwritten slot is 8 elements.
+MUT_MIN = {
+    "eps_1e-5": ("plain", 100, 0),
+    "no_round_bonus_v": ("plain", 800, 0),
+    "no_round_a_minus_1": ("plain", 2000, 20000),
+    "no_round_vgate": ("plain", 2000, 30000),
+    "ka_kk_swapped": ("plain", 10000, 200000),
+    "half_wave": ("plain", 900, 16000),
+    "heads_swapped_between_slots": ("plain", 0, 8000),
+    "v_gate_at_layer0": ("plain-layer0", 10000, 200000),
+    "elapsed_off_by_one": ("plain", 4000, 100000),
+    "untouched_slot_overwritten": ("plain", 0, 8),
+    "one_pass_variance": ("offset", 24, 0),                # the issue's bar: at least 1 % of 2 304 elements
+}
+
+
+def mut_case(name):
+    key = "mut:" + name
+    if key not in _CACHE:
+        inp, _ = R.make_inputs(**MUT_CASES[name])
+        _CACHE[key] = (inp, R.reference(inp))
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("mutant", R.MUTANTS)
+def test_mutant_is_rejected(mutant):
+    cname, min_out, min_state = MUT_MIN[mutant]
+    inp, ref = mut_case(cname)
+    good, S_good = R.emulate(inp, "butterfly")
+    assert R.check(good, ref["lo"], ref["hi"])["bad"] == 0 and np.array_equal(bits(S_good), bits(ref["state"]))
+    out, S = R.emulate(inp, "butterfly", mutant)
+    res = R.check(out, ref["lo"], ref["hi"])
+    n_state = int((bits(S) != bits(ref["state"])).sum())
+    print(f"{mutant} on {cname}: {res['bad']} of {res['n']} out elements rejected, {n_state} of {S.size} state elements differ")
+    assert res["bad"] >= min_out and n_state >= min_state
+    assert res["bad"] + n_state > 0
+
+
+@pytest.mark.parametrize("mutant", ["eps_1e-5", "no_round_bonus_v", "no_round_vgate", "half_wave"])
+@pytest.mark.parametrize("cname", ["offset", "outlier"])
+def test_mutants_are_rejected_in_the_other_regimes_too(cname, mutant):
+    inp, ref = mut_case(cname)
+    out, S = R.emulate(inp, "butterfly", mutant)
+    res = R.check(out, ref["lo"], ref["hi"])
+    print(f"{mutant} on {cname}: {res['bad']} of {res['n']} out elements rejected")
+    assert res["bad"] >= 10
+
+
+def test_one_pass_variance_passes_on_zero_mean_inputs_and_fails_on_offset_ones():
+    """Why the offset regime exists: E[y^2] - mean^2 is indistinguishable from the two-pass variance on zero-mean heads."""
+    inp, ref = mut_case("plain")
+    out, _ = R.emulate(inp, "butterfly", "one_pass_variance")
+    plain_bad = R.check(out, ref["lo"], ref["hi"])["bad"]
+    inp, ref = mut_case("offset")
+    out, _ = R.emulate(inp, "butterfly", "one_pass_variance")
+    res = R.check(out, ref["lo"], ref["hi"])
+    print(f"one-pass variance: plain {plain_bad} rejected, offset {res['bad']} of {res['n']}")
+    assert res["bad"] >= 0.01 * res["n"]
+    y = ref["y"].astype(np.float64).reshape(-1, 64)
+    assert np.median(np.abs(y.mean(-1)) / y.std(-1)) > 20          # the regime is what it claims to be
+
+
+def test_sixty_four_chained_steps_stay_finite_and_exact_in_every_order():
+    S_ref = None
+    for step, (inp, ref) in enumerate(R.chain_inputs(steps=64)):
+        assert ref["amb_gate"] == 0 and ref["amb_norm"] == 0
+        if step % 16 == 15:                                          # (the emulation is the slow part: every 16th step)
+            for order in ("butterfly", "sequential"):
+                out, S = R.emulate(inp, order)
+                assert np.array_equal(bits(S), bits(ref["state"]))
+                R.assert_check(out, ref["lo"], ref["hi"], name=f"step {step} {order}")
+        S_ref = ref["state"]
+        assert np.isfinite(ref["lo"].astype(F32)).all() and np.isfinite(ref["hi"].astype(F32)).all()
+    assert np.isfinite(S_ref.astype(F32)).all()
+
+
+def test_edge_case_reference_has_nan_exactly_in_the_zero_head():
+    inp, st = R.make_inputs(**R.EDGE_CASE)
+    ref = R.reference(inp)
+    assert ref["amb_gate"] == 0
+    b, hd = inp["zero_head"]
+    want_state = np.zeros(ref["state"].shape, bool)
+    want_state[b, hd] = True
+    want_out = np.zeros(ref["lo"].shape, bool)
+    want_out[b, :, hd * 64:(hd + 1) * 64] = True
+    assert np.array_equal(np.isnan(ref["state"]), want_state)
+    assert np.array_equal(np.isnan(ref["lo"]), want_out) and np.array_equal(np.isnan(ref["hi"]), want_out)
+    fin = ~want_out
+    assert np.isfinite(ref["lo"][fin].astype(F32)).all() and np.isfinite(ref["hi"][fin].astype(F32)).all()
+    for order in ("butterfly", "sequential"):
+        out, S = R.emulate(inp, order)
+        assert np.array_equal(np.isnan(S), want_state)
+        assert np.array_equal(bits(S)[~want_state], bits(ref["state"])[~want_state])
+        R.assert_check(out, ref["lo"], ref["hi"], name=order)
+    out, S = oracle_path(inp)
+    assert np.array_equal(bits(S)[~want_state], bits(ref["state"])[~want_state])
+    R.assert_check(out, ref["lo"], ref["hi"], name="oracle")
+
+
+def test_check_orders_zeroes_and_compares_nan_by_mask():
+    f = lambda *v: np.array(v, dtype=F16)
+    assert R.check(f(0.0), f(-0.0), f(0.0))["bad"] == 0 and R.check(f(-0.0), f(-0.0), f(0.0))["bad"] == 0
+    assert R.check(f(-0.0), f(0.0), f(0.0))["bad"] == 1                 # one admissible pattern: bits must match
+    assert R.check(f(1.0), f(1.0), f(1.0))["bad"] == 0
+    assert R.check(f(1.001), f(1.0), f(1.0))["bad"] == 1
+    assert R.check(f(np.nan), f(1.0), f(1.0))["bad"] == 1 and R.check(f(1.0), f(np.nan), f(np.nan))["bad"] == 1
+    nan2 = np.array([0x7E00, 0xFFFF], np.uint16).view(F16)              # payload and sign of a NaN do not matter
+    assert R.check(nan2, f(np.nan, np.nan), f(np.nan, np.nan))["bad"] == 0
+    res = R.check(f(-2.0, 3.0), f(-1.0, 1.0), f(1.0, 2.0))
+    assert res["bad"] == 2 and res["worst"] == 1024 and "group 0" in res["msg"]
+
+
+def test_activation_tables():
+    """Few binary16 inputs have an ambiguous sigmoid / tanh, saturated and special inputs have none."""
+    for kind, fn in (("sigmoid", lambda x: 1 / (1 + np.exp(-x))), ("tanh", np.tanh)):
+        amb = R.act_ambiguous(kind)
+        print(kind, "ambiguous inputs:", int(amb.sum()), "of 63488 finite")
+        assert 0 < amb.sum() <= 100
+        lo, hi = R.act_table(kind)
+        x = np.arange(65536, dtype=np.uint16).view(F16)
+        assert np.array_equal(np.isnan(lo), np.isnan(x)) and np.array_equal(np.isnan(hi), np.isnan(x))
+        with np.errstate(over="ignore"):
+            near = fn(x.astype(np.float64)).astype(F16)
+        ok = ~np.isnan(x)
+        assert (R.key(lo[ok]) <= R.key(near[ok])).all() and (R.key(near[ok]) <= R.key(hi[ok])).all()
+        assert (R.key(hi[ok]) - R.key(lo[ok]) <= 1).all()
+    lo, hi = R.act_table("sigmoid")
+    for v, want in ((60000.0, 1.0), (-60000.0, 0.0), (np.inf, 1.0), (-np.inf, 0.0), (0.0, 0.5), (-0.0, 0.5)):
+        i = int(bits(np.array([v], F16))[0])
+        assert bits(lo[i:i + 1])[0] == bits(hi[i:i + 1])[0] == bits(np.array([want], F16))[0]
+    g, n = R.guard_preact(np.arange(65536, dtype=np.uint16).view(F16)[:0x7C00])
+    assert n == int(R.act_ambiguous("sigmoid")[:0x7C00].sum()) and not R.act_ambiguous("sigmoid")[bits(g)].any()
+
+
+def test_exact_sum_lemma_and_norm_interval_against_binary32_orders():
+    """The derived bounds hold for three binary32 orders on adversarial magnitudes (wide dynamic range within a head)."""
+    rng = np.random.default_rng(5)
+    t = (rng.standard_normal((4000, 64)) * 10.0 ** rng.uniform(-3, 2, (4000, 64))).astype(F16)
+    s, e = R.head_sum(t)
+    n_lo, n_hi = R.norm_interval(t)
+    for order in ("pairwise", "butterfly", "sequential"):
+        got = R.sum32(t.astype(F32), order)[:, 0].astype(np.float64)
+        assert (np.abs(got - s) <= e).all()
+        nrm = np.sqrt(R.sum32(t.astype(F32) ** 2, order)[:, 0]).astype(F16)
+        assert (R.key(n_lo) <= R.key(nrm)).all() and (R.key(nrm) <= R.key(n_hi)).all()
+    big = (50 + rng.standard_normal((1000, 64))).astype(F16)             # multiples of 2^-5: every order is exact
+    s, e = R.head_sum(big)
+    assert (e <= 1e-9).all()
+    for order in ("pairwise", "butterfly", "sequential"):
+        assert np.array_equal(R.sum32(big.astype(F32), order)[:, 0].astype(np.float64), s)
+
+
+LN_CASES = [("offset", 3, 1, 768), ("offset", 5, 5, 4096), ("outlier", 4, 5, 768), ("outlier", 200, 1, 4096), ("plain", 3, 4, 768)]
+
+
+@pytest.mark.parametrize("regime,B,T,C", LN_CASES)
+def test_layer_norm_reference_accepts_binary32_orders_and_rejects_mutants(regime, B, T, C):
+    """LayerNorm + token shift: the same interval machinery with one group of C channels.  Two binary32 orders pass, a skipped
+    rounding in the lerp is rejected everywhere, the one-pass variance in the offset regime."""
+    li = R.ln_inputs(B, T, C, regime, seed=B + T + C)
+    ref = R.ln_mix_reference(li["x"], li["delta"], li["w"], li["b"], li["prev"], li["mix"], slot_idx=li["slot_idx"])
+    wc = R.interval_width(ref["cur"][0], ref["cur"][1])
+    wo = R.interval_width(*ref["out"])
+    print(f"LN {regime} B{B} T{T} C{C}: cur single {np.mean(wc == 1):.4f} wide {np.mean(wc > 2):.4f}; out single {np.mean(wo == 1):.4f} "
+          f"wide {np.mean(wo > 2):.4f}")
+    # No sharpness cap here, unlike the head-sized groups: an any-order bound over C terms is gamma_(C-1) relative -- 4.6e-5 at
+    # C = 768, 2.4e-4 at C = 4096, against half a binary16 ulp of 2.4e-4 .. 4.9e-4 -- so a large share of the normalised values
+    # is ambiguous by one half unless the row sum is exact (the offset regime).  The check stays rigorous, only less sharp; what
+    # it still rejects is asserted below, the shares are in DESIGN.md.
+    assert np.isfinite(ref["out"][0].astype(F32)).all() and np.isfinite(ref["out"][1].astype(F32)).all()
+    for order in ("pairwise", "lanes"):
+        out, cur = R.ln_emulate(li, order)
+        R.assert_check(cur, ref["cur"][0], ref["cur"][1], name=f"cur {order}", group=C)
+        R.assert_check(out, *ref["out"], name=f"out {order}", group=C)
+    out, _ = R.ln_emulate(li, "lanes", "no_round_lerp")
+    res = R.check(out, *ref["out"], group=C)
+    print(f"   no_round_lerp rejected on {res['bad']} of {res['n']}")
+    assert res["bad"] >= 0.02 * res["n"]
+    if regime == "offset":
+        out, cur = R.ln_emulate(li, "lanes", "one_pass_variance")
+        res = R.check(cur, ref["cur"][0], ref["cur"][1], group=C)
+        print(f"   one_pass_variance rejected on {res['bad']} of {res['n']}")
+        assert res["bad"] >= 0.01 * res["n"]
