@@ -28,6 +28,7 @@ DEFAULT_SAMPLING_CONFIG: Dict[str, Any] = {
     "max_tokens": 8192,
 }
 LOGIT_BIAS_MAX = 1024          # entries of one request's logit_bias (the worker's per-slot list capacity)
+GUIDE_MAX_STATES = 4096        # states of one guide's byte DFA (chirrup_amd/guided.py); a state is one row of the worker's guide pool
 
 
 class FinishReason(enum.IntEnum):
@@ -112,9 +113,14 @@ class Task:
     # from Philox stream j, so choice 0 reproduces the single request with the same seed
     choice_index: int = 0
     siblings: List["Task"] = field(default_factory=list)
+    # guided decoding: a guided.ByteDFA the generated text must match in full.  Each decode step masks the tokens whose bytes would
+    # leave the automaton; a stop token is allowed in accepting states only, so "stop" means the text matches (max_tokens may still
+    # cut it short).  Needs stop tokens and max_tokens > 0; logprobs still measure the raw output (DESIGN.md "Guided decoding")
+    guide: Any = None
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
+    error: Optional[str] = field(init=False, default=None)      # why the worker refused the request (it then ends aborted)
     generated_tokens: List[int] = field(init=False, default_factory=list)
     decoded_texts: List[str] = field(init=False, default_factory=list)
 
@@ -143,6 +149,13 @@ class Task:
                 raise ValueError(f"logit_bias: the bias of token {t} is not a finite number")
             checked[t] = float(v)
         self.logit_bias = checked
+        if self.guide is not None:
+            if not all(hasattr(self.guide, a) for a in ("next", "accept", "key")):
+                raise ValueError("guide must be a guided.ByteDFA (compile_regex, compile_choice)")
+            if not self.stop_tokens:
+                raise ValueError("a guided request needs stop tokens: the end of a constrained text is a stop token")
+            if self.max_tokens == 0 or self.prompt_logprobs is not None:
+                raise ValueError("a guide applies to generated tokens only: not with max_tokens=0 or prompt_logprobs")
         self.check_group()
 
     def check_group(self) -> None:

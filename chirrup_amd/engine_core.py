@@ -15,6 +15,7 @@ an interpreter with a GIL.
 """
 import sys
 import asyncio
+import json
 import queue
 import threading
 import uuid
@@ -22,6 +23,42 @@ from typing import Any, AsyncIterator, Callable, Dict, List, Optional
 
 from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, ModelLoadConfig, Task
 from .interface import AsyncEngineCompletion
+
+GUIDE_CACHE_SIZE = 64          # compiled guides kept by the engine, least recently used first out
+
+
+def _compiled_guide(cache: Dict[Any, Any], guided_regex, guided_choice, guided_json):
+    """The ByteDFA of the one guided_* argument given (None when none is): compiled here, on the caller's side, so that a bad
+    pattern raises GuideError before anything is queued; a small LRU keyed by the source spares the recompilation."""
+    from .guided import GuideError, compile_choice, compile_regex, schema_to_regex
+
+    given = [k for k, v in (("guided_regex", guided_regex), ("guided_choice", guided_choice), ("guided_json", guided_json)) if v is not None]
+    if not given:
+        return None
+    if len(given) > 1:
+        raise GuideError(f"at most one of guided_regex, guided_choice and guided_json may be given, got {' and '.join(given)}")
+    try:
+        if guided_regex is not None:
+            src = ("regex", guided_regex)
+        elif guided_choice is not None:
+            src = ("choice", tuple(guided_choice))
+        else:
+            src = ("json", json.dumps(guided_json, ensure_ascii=False))
+        hash(src)
+    except (TypeError, ValueError) as e:
+        raise GuideError(f"{given[0]}: {e}") from None
+    dfa = cache.pop(src, None)
+    if dfa is None:
+        if guided_regex is not None:
+            dfa = compile_regex(guided_regex)
+        elif guided_choice is not None:
+            dfa = compile_choice(list(guided_choice))
+        else:
+            dfa = compile_regex(schema_to_regex(guided_json))
+    cache[src] = dfa                                   # (re-inserted: the most recently used is last)
+    while len(cache) > GUIDE_CACHE_SIZE:
+        cache.pop(next(iter(cache)))
+    return dfa
 
 
 class ThreadSafeAsyncQueue:
@@ -88,6 +125,7 @@ class AsyncEngineCore:
         self.max_choices = None                       # a worker's slot count (batch_size - 1), set by init(): the largest n of completions()
         self.tokenizer = tokenizer
         self._worker_factory = worker_factory
+        self._guide_cache: Dict[Any, Any] = {}
 
     def _make_worker(self, **kw):
         kw.update(self._worker_kwargs)
@@ -219,7 +257,12 @@ class AsyncEngineCore:
                    max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], task_id: Optional[str] = None,
                    cache_prefill: bool = False, cache_prefill_padding: int = 0,
                    return_logits: bool = False, logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
-                   logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None) -> AsyncEngineCompletion:
+                   logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None,
+                   guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
+                   guided_json: Optional[Dict[str, Any]] = None) -> AsyncEngineCompletion:
+        """guided_regex / guided_choice / guided_json (at most one): the generated text must match the pattern, be one of the strings,
+        or be compact JSON that satisfies the schema (chirrup_amd/guided.py for the subsets; GuideError, a ValueError, otherwise).  The
+        request then ends "stop" exactly when its text matches; it needs stop tokens."""
         assert not (state is not None and prefill_tokens is None), "prefill_tokens cannot be None when state is not None"
         if not self.is_initialized:
             raise RuntimeError("Engine not initialized")
@@ -228,6 +271,7 @@ class AsyncEngineCore:
         bad = [t for t in (logit_bias or {}) if isinstance(t, int) and self.vocab_size is not None and t >= self.vocab_size]
         if bad:
             raise ValueError(f"logit_bias: token id {bad[0]} is outside the vocabulary (size {self.vocab_size})")
+        guide = _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json)
         if not prefill_tokens:
             prefill_tokens = self.tokenizer.encode(prompt_str)
         task_id = task_id or str(uuid.uuid4())
@@ -244,7 +288,13 @@ class AsyncEngineCore:
                                      stop_tokens=stop_tokens, forbidden_tokens=forbidden_tokens, max_tokens=max_tokens,
                                      cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                                      return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
-                                     logit_bias=logit_bias, prompt_logprobs=prompt_logprobs)
+                                     logit_bias=logit_bias, prompt_logprobs=prompt_logprobs, guide=guide)
+
+    def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
+                      guided_json: Optional[Dict[str, Any]] = None):
+        """The compiled guide completion() would use for these arguments (None without any); GuideError for a bad one.  A front end
+        calls it to refuse a request before it starts answering."""
+        return _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json)
 
     def completions(self, prompt_str: str, prefill_tokens: Optional[List[int]] = None, n: int = 1, **kw) -> List[AsyncEngineCompletion]:
         """n parallel choices of one prompt: completion()'s keywords, one AsyncEngineCompletion per choice (index order).  Starting

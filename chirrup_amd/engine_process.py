@@ -32,8 +32,8 @@ from .remote_arena import WIRE_KEY, PeerArenas, RemoteStateRef, is_wire_row
 _TASK_FIELDS = ("prompt_str", "prefill_tokens", "state", "task_id", "priority", "temperature", "top_p", "top_k", "presence_penalty",
                 "frequency_penalty", "penalty_decay", "max_tokens", "stop_tokens", "forbidden_tokens", "cache_prefill",
                 "cache_prefill_padding", "return_logits", "logprobs", "top_logprobs", "seed", "logit_bias",
-                "prompt_logprobs", "choice_index")
-_RESULT_FIELDS = ("request_status", "generated_tokens", "decoded_texts", "prefill_tokens")
+                "prompt_logprobs", "choice_index", "guide")
+_RESULT_FIELDS = ("request_status", "generated_tokens", "decoded_texts", "prefill_tokens", "error")
 
 
 def task_to_wire(task: Task) -> Dict[str, Any]:
@@ -443,7 +443,7 @@ class ResultRouter(threading.Thread):
             if kind == "task_completed":
                 task.request_status = RequestStatus(payload["request_status"])
                 task.generated_tokens, task.decoded_texts = payload["generated_tokens"], payload["decoded_texts"]
-                task.prefill_tokens = payload["prefill_tokens"]
+                task.prefill_tokens, task.error = payload["prefill_tokens"], payload.get("error")
                 task.output_queue.put_nowait(("task_completed", task))
             else:
                 task.output_queue.put_nowait((kind, payload))

@@ -22,7 +22,7 @@ class AsyncEngineCompletion:
                  max_tokens: Optional[int] = DEFAULT_SAMPLING_CONFIG["max_tokens"], cache_prefill: bool = False,
                  cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None,
                  logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
-                 logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None):
+                 logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None, guide=None):
         self.task_id = task_id
         # the worker polls it for ("abort", None); a process-mode engine passes a channel that reaches the worker's process
         self.task_event_queue = task_event_queue if task_event_queue is not None else queue.Queue()
@@ -34,11 +34,12 @@ class AsyncEngineCompletion:
                          stop_tokens=stop_tokens, forbidden_tokens=list(forbidden_tokens or []),
                          cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                          return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
-                         logit_bias=dict(logit_bias or {}), prompt_logprobs=prompt_logprobs)
+                         logit_bias=dict(logit_bias or {}), prompt_logprobs=prompt_logprobs, guide=guide)
         self._task_queue = task_queue
         # one choice of a request with parallel choices (AsyncEngineCore.completions): the callable that submits the whole group --
         # once, whichever of its choices starts first
         self.group_start = None
+        self.error: Optional[str] = None           # why the worker refused the request (("error", reason), then it ends aborted)
         self._submitted = False
         self.is_finished = False
 
@@ -68,6 +69,9 @@ class AsyncEngineCompletion:
                 return ("cache_prefill", payload)
             if kind == "prompt_logprobs":
                 return ("prompt_logprobs", payload)
+            if kind == "error":
+                self.error = payload
+                continue
             if kind == "task_completed":
                 self.is_finished = True
                 self.task = payload

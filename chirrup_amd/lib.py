@@ -62,6 +62,9 @@ SIGNATURES = {
     "rwkv7_token_logprobs": (_i, [_i, _i, _i] + [_vp] * 7),
     "rwkv7_seeded_uniform": (_i, [_i] + [_vp] * 7),
     "rwkv7_apply_logit_bias": (_i, [_i, _i, _i] + [_vp] * 6),
+    "rwkv7_guide_build": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "rwkv7_guide_apply": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "rwkv7_guide_advance": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rwkv7_embed_rows": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _vp]),
     "rwkv7_advance_elapsed": (_i, [_i, _i, _vp, _vp, _vp]),
     "rwkv7_copy_slot_rows": (_i, [_i, _i, _vp, _vp, _vp, _vp]),

@@ -1330,6 +1330,150 @@ def _apply_logit_bias_host(logits, slot_idx, counts, ids, values):
         row[t[fin]] = np.clip(lv[fin] + b[fin], np.float32(-65504), np.float32(65504)).astype(np.float16)
 
 
+def _guide_pool_shapes(guide_next, guide_allow, V):
+    if guide_next.dtype != torch.int32 or guide_next.dim() != 2 or guide_next.shape[1] != 256 or not guide_next.is_contiguous():
+        raise _lib.ChirrupAmdError("guide_next: expected contiguous int32 [P, 256]")
+    if guide_allow is not None and (guide_allow.dtype != torch.int32 or guide_allow.dim() != 2 or not guide_allow.is_contiguous()
+                                    or guide_allow.shape[0] != guide_next.shape[0] or guide_allow.shape[1] * 32 != V):
+        raise _lib.ChirrupAmdError("guide_allow: expected contiguous int32 [P, V / 32] (the uint32 bitmap words)")
+
+
+def guide_build(S: int, row0: int, guide_next, tok_off, tok_bytes, special, accept, guide_allow) -> None:
+    """Fills the bitmap rows [row0, row0 + S) of a guide pool (include/chirrup_amd.h: rwkv7_guide_build): bit (s, t) of guide_allow
+    int32 [P, V/32] (uint32 words, bit t % 32 of word t // 32) is set iff token t has bytes (tok_off int32 [V + 1] into tok_bytes
+    uint8) and walking them from row row0 + s through guide_next int32 [P, 256] (absolute rows, -1 dead) never dies; for the ids in
+    `special` (int32, the request's stop tokens) the bit is accept[s] (uint8 [S]) and the bytes are not walked.  V % 64 == 0.  CPU
+    tensors take the numpy form (fake backends, and the reference the kernel is tested against); GPU tensors always take the kernel."""
+    V = tok_off.numel() - 1
+    _guide_pool_shapes(guide_next, guide_allow, V)
+    P = guide_next.shape[0]
+    if V <= 0 or V % 64 or S < 0 or row0 < 0 or row0 + S > P or accept.numel() != S or accept.dtype != torch.uint8:
+        raise _lib.ChirrupAmdError(f"guide_build: V = {V} must be a positive multiple of 64, rows [{row0}, {row0 + S}) inside the pool "
+                                   f"of {P}, accept uint8 [{S}]")
+    if tok_off.dtype != torch.int32 or tok_bytes.dtype != torch.uint8 or special.dtype != torch.int32:
+        raise _lib.ChirrupAmdError("tok_off / special: expected int32, tok_bytes: uint8")
+    if S == 0:
+        return
+    if not guide_next.is_cuda:
+        _guide_build_host(S, row0, guide_next, tok_off, tok_bytes, special, accept, guide_allow)
+        return
+    for name, t in (("tok_off", tok_off), ("tok_bytes", tok_bytes), ("special", special), ("accept", accept), ("guide_allow", guide_allow)):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_guide_build(S, row0, P, V, _ptr(guide_next), _ptr(tok_off), _ptr(tok_bytes), special.numel(),
+                                       _ptr(special) if special.numel() else None, _ptr(accept), _ptr(guide_allow), _stream())
+    _lib.check(rc, "rwkv7_guide_build")
+
+
+def _guide_build_host(S, row0, guide_next, tok_off, tok_bytes, special, accept, guide_allow, chunk: int = 32):
+    import numpy as np
+
+    nxt, off, by = guide_next.numpy(), tok_off.numpy().astype(np.int64), tok_bytes.numpy()
+    P, V = nxt.shape[0], off.shape[0] - 1
+    lens = off[1:] - off[:-1]
+    defined = np.nonzero(lens > 0)[0]
+    sp = np.array([t for t in special.tolist() if 0 <= t < V], np.int64)
+    acc = accept.numpy() != 0
+    allow = guide_allow.numpy()                              # a view: rows are written in place
+    for s0 in range(0, S, chunk):
+        c = min(chunk, S - s0)
+        ok = np.zeros((c, V), np.bool_)
+        si = np.repeat(np.arange(c), len(defined))          # the (state, token) pairs whose walk is still alive
+        ti = np.tile(defined, c)
+        cur = (row0 + s0 + si).astype(np.int64)
+        pos = 0
+        while len(ti):
+            cur = nxt[cur, by[off[ti] + pos]].astype(np.int64)
+            keep = (cur >= 0) & (cur < P)
+            si, ti, cur = si[keep], ti[keep], cur[keep]
+            pos += 1
+            done = lens[ti] == pos
+            ok[si[done], ti[done]] = True
+            si, ti, cur = si[~done], ti[~done], cur[~done]
+        if len(sp):
+            ok[:, sp] = acc[s0:s0 + c, None]
+        allow[row0 + s0:row0 + s0 + c] = np.packbits(ok, axis=1, bitorder="little").view("<u4").view(np.int32)
+
+
+def guide_apply(logits, rows, slot_idx, guide_state, guide_allow) -> None:
+    """logits[r][t] = -inf where the state row of r's slot forbids token t, for the listed rows r (include/chirrup_amd.h:
+    rwkv7_guide_apply): s = slot_idx[r] (r without slot_idx), st = guide_state[s]; rows of slots with st < 0 are untouched.  fp16
+    logits [n, V] in place, V % 32 == 0; rows int32; guide_allow int32 [P, V/32].  CPU tensors take the numpy form."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or not logits.is_contiguous():
+        raise _lib.ChirrupAmdError("logits: expected contiguous fp16 [n,V]")
+    n, V = logits.shape
+    if V % 32 or guide_allow.dtype != torch.int32 or guide_allow.dim() != 2 or guide_allow.shape[1] * 32 != V or not guide_allow.is_contiguous():
+        raise _lib.ChirrupAmdError("guide_allow: expected contiguous int32 [P, V / 32], V % 32 == 0")
+    if rows.dtype != torch.int32 or guide_state.dtype != torch.int32 or (slot_idx is not None and (slot_idx.dtype != torch.int32 or slot_idx.numel() != n)):
+        raise _lib.ChirrupAmdError("rows / slot_idx / guide_state: expected int32 (slot_idx with one entry per logits row)")
+    if rows.numel() == 0:
+        return
+    if not logits.is_cuda:
+        _guide_apply_host(logits, rows, slot_idx, guide_state, guide_allow)
+        return
+    for name, t in (("rows", rows), ("guide_state", guide_state), ("guide_allow", guide_allow)) + ((("slot_idx", slot_idx),) if slot_idx is not None else ()):
+        _chk(t, name, torch.int32)
+    rc = _lib.load().rwkv7_guide_apply(rows.numel(), n, V, guide_allow.shape[0], _ptr(logits), _ptr(rows), _ptr(slot_idx),
+                                       guide_state.numel(), _ptr(guide_state), _ptr(guide_allow), _stream())
+    _lib.check(rc, "rwkv7_guide_apply")
+
+
+def _guide_apply_host(logits, rows, slot_idx, guide_state, guide_allow):
+    import numpy as np
+
+    n, V = logits.shape
+    lg, allow, P = logits.numpy().view(np.uint16), guide_allow.numpy(), guide_allow.shape[0]
+    slots = slot_idx.tolist() if slot_idx is not None else list(range(n))
+    for r in rows.tolist():
+        if not 0 <= r < n or not 0 <= slots[r] < guide_state.numel():
+            continue
+        st = int(guide_state[slots[r]])
+        if 0 <= st < P:
+            bits = np.unpackbits(allow[st].view(np.uint8), bitorder="little")[:V].astype(np.bool_)
+            lg[r][~bits] = 0xFC00                           # binary16 -inf
+
+
+def guide_advance(rows, slot_idx, ids, tok_off, tok_bytes, guide_next, guide_state) -> None:
+    """Moves the guide state of the listed rows' slots by the sampled ids (include/chirrup_amd.h: rwkv7_guide_advance): for r in
+    rows, s = slot_idx[r] (r without), guide_state[s] = the row after walking the bytes of ids[r] through guide_next; unchanged
+    when the slot is unconstrained (-1), the walk dies, or the id has no bytes / is outside the vocabulary.  CPU tensors take the
+    numpy form."""
+    V = tok_off.numel() - 1
+    _guide_pool_shapes(guide_next, None, V)
+    if any(t.dtype != torch.int32 for t in (rows, ids, tok_off, guide_state)) or tok_bytes.dtype != torch.uint8 or (
+            slot_idx is not None and (slot_idx.dtype != torch.int32 or slot_idx.numel() != ids.numel())):
+        raise _lib.ChirrupAmdError("rows / slot_idx / ids / tok_off / guide_state: expected int32 (slot_idx with one entry per id), tok_bytes: uint8")
+    if rows.numel() == 0:
+        return
+    if not guide_next.is_cuda:
+        _guide_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, guide_next, guide_state)
+        return
+    for name, t in (("rows", rows), ("ids", ids), ("tok_off", tok_off), ("tok_bytes", tok_bytes), ("guide_state", guide_state)) + (
+            (("slot_idx", slot_idx),) if slot_idx is not None else ()):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_guide_advance(rows.numel(), ids.numel(), V, guide_next.shape[0], _ptr(rows), _ptr(slot_idx), guide_state.numel(),
+                                         _ptr(ids), _ptr(tok_off), _ptr(tok_bytes), _ptr(guide_next), _ptr(guide_state), _stream())
+    _lib.check(rc, "rwkv7_guide_advance")
+
+
+def _guide_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, guide_next, guide_state):
+    off, by, V, P = tok_off.tolist(), tok_bytes.numpy(), tok_off.numel() - 1, guide_next.shape[0]
+    id_list = ids.tolist()
+    slots = slot_idx.tolist() if slot_idx is not None else list(range(len(id_list)))
+    for r in rows.tolist():
+        if not 0 <= r < len(id_list) or not 0 <= slots[r] < guide_state.numel():
+            continue
+        s, t = slots[r], id_list[r]
+        st = int(guide_state[s])
+        if not 0 <= st < P or not 0 <= t < V or off[t + 1] <= off[t]:
+            continue
+        for b in by[off[t]:off[t + 1]].tolist():
+            st = int(guide_next[st, b])
+            if not 0 <= st < P:
+                break
+        else:
+            guide_state[s] = st
+
+
 def lora_act_(hbuf, first_plane: int) -> None:
     """hbuf [n, rows, D] fp16, planes first_plane.. of [v, w, a, g]: tanh on w, sigmoid on g."""
     _chk16("hbuf", hbuf)

@@ -22,6 +22,7 @@ from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, model_validator
 
 from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, LOGIT_BIAS_MAX, RequestStatus
+from .guided import GuideError
 from .state_cache import SimpleStateCache
 
 KEEP_ALIVE_S = 10.0
@@ -46,6 +47,36 @@ def _check_logit_bias(logit_bias: Optional[Dict[str, float]]) -> None:
             raise ValueError(f"logit_bias: the bias of token {key} is outside [-100, 100]")
     if len(seen) > LOGIT_BIAS_MAX:
         raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries")
+
+
+def guided_arguments(engine, request, thinking: bool = False) -> Dict[str, Any]:
+    """The guided_* keywords of engine.completion() for a request's guided_regex / guided_choice / response_format, checked and
+    compiled now: every refusal is a 400 with the reason (more than one of them, json_object, a pattern or schema outside the
+    supported subset, a guide on a model variant that opens with a reasoning block)."""
+    kw: Dict[str, Any] = {}
+    if request.guided_regex is not None:
+        kw["guided_regex"] = request.guided_regex
+    if request.guided_choice is not None:
+        kw["guided_choice"] = request.guided_choice
+    rf = request.response_format
+    if rf is not None and rf.get("type") != "text":
+        if rf.get("type") == "json_object":
+            raise HTTPException(status_code=400, detail="response_format json_object is not supported: arbitrary JSON nests without bound "
+                                "and is not a regular language; give a schema with response_format json_schema")
+        schema = (rf.get("json_schema") or {}).get("schema") if isinstance(rf.get("json_schema"), dict) else None
+        if rf.get("type") != "json_schema" or not isinstance(schema, dict):
+            raise HTTPException(status_code=400, detail="response_format: expected {\"type\": \"text\"} or {\"type\": \"json_schema\", "
+                                "\"json_schema\": {\"schema\": {...}}}")
+        kw["guided_json"] = schema
+    if len(kw) > 1:
+        raise HTTPException(status_code=400, detail=f"at most one of guided_regex, guided_choice and response_format json_schema may be given, got {len(kw)}")
+    if kw and thinking:
+        raise HTTPException(status_code=400, detail="guided decoding cannot follow a reasoning block: use a model without the :thinking suffix")
+    try:
+        engine.compile_guide(**kw)
+    except GuideError as e:
+        raise HTTPException(status_code=400, detail=f"guided decoding: {e}")
+    return kw
 
 
 class ChatCompletionRequest(BaseModel):                      # api_model.py:14-62: same fields, defaults and ranges
@@ -73,6 +104,11 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     # n choices of the prompt (prefilled once; at most a worker's slot count, else 400): choices[j] with index j, a seeded choice j
     # draws from its own Philox stream (choice 0 equals the n = 1 request with the same seed)
     n: int = Field(1, ge=1, le=128)
+    # guided decoding (at most one): the content must match the regular expression / be one of the strings (extension fields, as in
+    # other open servers), or OpenAI's response_format {"type": "json_schema", "json_schema": {"schema": {...}}}
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[List[str]] = None
+    response_format: Optional[Dict[str, Any]] = None
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):
@@ -113,6 +149,9 @@ class CompletionRequest(BaseModel):
     cache_prefill: bool = True
     n: int = 1
     best_of: Optional[int] = None
+    guided_regex: Optional[str] = None
+    guided_choice: Optional[List[str]] = None
+    response_format: Optional[Dict[str, Any]] = None
 
     @model_validator(mode="after")
     def _fields(self):
@@ -252,6 +291,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         vocab = getattr(engine, "vocab_size", None)
         if vocab is not None and bias and max(bias) >= vocab:
             raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        guided = guided_arguments(engine, request, thinking="thinking" in request.model.split(":"))
         n = request.n
         if n > 1 and n > (getattr(engine, "max_choices", None) or 1):
             raise HTTPException(status_code=400, detail=f"n = {n} exceeds the {getattr(engine, 'max_choices', None) or 1} choices a worker holds")
@@ -271,7 +311,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                       cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
                       **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}),
                       **({"seed": request.seed} if request.seed is not None else {}),
-                      **({"logit_bias": bias} if bias else {}))
+                      **({"logit_bias": bias} if bias else {}), **guided)
             choices = engine.completions(n=n, **kw) if n > 1 else [engine.completion(**kw)]      # one prefill for the n choices
         except HTTPException:
             raise
@@ -302,6 +342,8 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                     q.put_nowait(chunk({"content": piece} if st == "content" else {"content": "", "reasoning_content": piece},
                                        logprobs=pending, index=index))
                     pending = []
+            if completion.error:                                # the worker refused the request: reported in-band
+                raise RuntimeError(completion.error)
             if request.stream:
                 if pending:
                     q.put_nowait(chunk({"content": ""}, logprobs=pending, index=index))
@@ -380,6 +422,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         vocab = getattr(engine, "vocab_size", None)
         if vocab is not None and bias and max(bias) >= vocab:
             raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        guided = guided_arguments(engine, request)
         k, skip = request.logprobs, (1 if request.pad_zero else 0)      # skip: the token 0 in front is fed, not echoed
         score_prompt = request.echo and k is not None
         try:
@@ -430,7 +473,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                                      **({"logprobs": True, "top_logprobs": k} if k is not None and request.max_tokens > 0 else {}),
                                      **({"prompt_logprobs": k} if score_prompt else {}),
                                      **({"seed": request.seed} if request.seed is not None else {}),
-                                     **({"logit_bias": bias} if bias else {}))
+                                     **({"logit_bias": bias} if bias else {}), **guided)
             completions_.append(comp)
             plp: List[Any] = [None] * len(toks)
             n_plp, gen, gen_text = 0, [], []
@@ -459,6 +502,8 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                     node = state_cache.cache(key, ev[1]["state"], return_trie_node=True)
                     if node is not None:
                         await state_cache.awake_hang_up_prefills(key)
+            if comp.error:
+                raise RuntimeError(comp.error)
             reason = RequestStatus.get_finished_reason(comp.task.request_status)
             finish = str(reason) if reason is not None else "stop"
             logprobs = None

@@ -42,6 +42,7 @@ import torch
 
 from . import ops
 from .core_structure import LOGIT_BIAS_MAX, ModelLoadConfig, RequestStatus, Task
+from .guided import GuideError, token_table
 from .samplers import is_greedy_row, sample_inverse_cdf, sample_logits_rwkv_pip_compatible
 
 
@@ -84,11 +85,82 @@ def _empty_slot() -> dict:
             "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0, "siblings": None, "orphan": False}
 
 
+class GuidePool:
+    """The guides of one worker (DESIGN.md "Guided decoding"): every guide in use or recently used is a contiguous range of rows of
+    ``next`` int32 [P, 256] (absolute rows, -1 dead) and ``allow`` int32 [P, V/32] (uint32 bitmap words: the tokens a state allows);
+    ``state`` int32 [slots] holds each slot's current row, -1 for an unconstrained slot.  A guide is cached under (guide.key, its
+    sorted stop tokens) -- the stop tokens decide the bitmaps -- with a reference count; when a new guide finds no free range, the
+    least recently used guides nobody holds are dropped until it fits.  The token byte table is uploaded once."""
+
+    def __init__(self, rows: int, n_slots: int, V: int, device, idx2token):
+        if V % 64:
+            raise GuideError(f"guided decoding needs a vocabulary size that is a multiple of 64, got {V}")
+        if not idx2token:
+            raise GuideError("guided decoding needs the tokenizer's byte table (idx2token)")
+        off, data = token_table(idx2token, V)
+        self.P, self.V, self.device = int(rows), V, device
+        self.tok_off, self.tok_bytes = torch.from_numpy(off).to(device), torch.from_numpy(data).to(device)
+        self.next = torch.full((self.P, 256), -1, dtype=torch.int32, device=device)
+        self.allow = torch.zeros((self.P, V // 32), dtype=torch.int32, device=device)
+        self.state = torch.full((n_slots,), -1, dtype=torch.int32, device=device)
+        self.entries: Dict[tuple, dict] = {}          # key -> {"row0", "S", "refs", "tick"}
+        self._tick = 0
+        self.builds = 0                               # guides built (a cache hit builds nothing)
+
+    def _place(self, S: int) -> Optional[int]:
+        at = 0
+        for e in sorted(self.entries.values(), key=lambda e: e["row0"]):      # first fit among the gaps
+            if e["row0"] - at >= S:
+                return at
+            at = e["row0"] + e["S"]
+        return at if self.P - at >= S else None
+
+    def acquire(self, guide, stop_tokens) -> Tuple[tuple, int]:
+        """(cache key, start row) of the guide for a request with these stop tokens, built when it is new; the caller holds one
+        reference until release(key).  GuideError when it cannot be placed or the vocabulary cannot realise it."""
+        key = (guide.key, tuple(sorted(int(t) for t in stop_tokens)))
+        self._tick += 1
+        e = self.entries.get(key)
+        if e is not None:
+            e["refs"] += 1
+            e["tick"] = self._tick
+            return key, e["row0"]
+        S = int(guide.next.shape[0])
+        row0 = self._place(S)
+        while row0 is None:
+            idle = [k for k, v in self.entries.items() if v["refs"] == 0]
+            if not idle:
+                raise GuideError(f"the guide pool ({self.P} rows) has no room for a guide of {S} states: "
+                                 f"{sum(v['S'] for v in self.entries.values())} rows are held by running requests")
+            del self.entries[min(idle, key=lambda k: self.entries[k]["tick"])]
+            row0 = self._place(S)
+        import numpy as np
+
+        # stream-ordered writes: rows of a dropped guide may still be read by a run-ahead row in flight, which runs first
+        self.next[row0:row0 + S] = torch.from_numpy(np.where(guide.next >= 0, guide.next + np.int32(row0), np.int32(-1)).astype(np.int32)).to(self.device)
+        accept = torch.from_numpy(np.ascontiguousarray(guide.accept).astype(np.uint8)).to(self.device)
+        special = torch.tensor(key[1], dtype=torch.int32).to(self.device)
+        ops.guide_build(S, row0, self.next, self.tok_off, self.tok_bytes, special, accept, self.allow)
+        self.builds += 1
+        # the one host synchronisation of the feature, once per new guide: a state that allows no token would leave its row with
+        # nothing to sample (the vocabulary cannot spell what the pattern asks for there)
+        empty = (self.allow[row0:row0 + S] == 0).all(dim=1)
+        if bool(empty.any()):
+            raise GuideError(f"the vocabulary cannot realise the pattern: state {int(empty.nonzero()[0])} of its automaton allows no token")
+        self.entries[key] = {"row0": row0, "S": S, "refs": 1, "tick": self._tick}
+        return key, row0
+
+    def release(self, key) -> None:
+        e = self.entries.get(key)
+        if e is not None and e["refs"] > 0:
+            e["refs"] -= 1
+
+
 class Worker:
     def __init__(self, worker_id: str, gpu_id: List[int], model_config: ModelLoadConfig, task_queue: queue.Queue,
                  master_event_queue: queue.Queue, worker_event_queue: Optional[queue.Queue], batch_size: int = 32,
                  model=None, tokenizer=None, penalize_argmax=None, state_cache_device=None, run_ahead: bool = True,
-                 state_arena=None, state_arena_rows: int = 0, peer_arenas=None):
+                 state_arena=None, state_arena_rows: int = 0, peer_arenas=None, guide_pool_rows: int = 16384):
         self.worker_id, self.gpu_id, self.model_config = worker_id, gpu_id, model_config
         self.task_queue, self.master_event_queue, self.worker_event_queue = task_queue, master_event_queue, worker_event_queue
         self.real_state_size = batch_size
@@ -130,6 +202,13 @@ class Worker:
         self.iterations = 0
         self._held = None                             # a group of parallel choices pulled before n slots were free
         self._groups: List[Tuple[int, Task]] = []     # (slot, choice-0 task) of the admitted groups that have not forked yet
+        # guided decoding: the pool (rows of automaton states: 8 KiB + 1 KiB per row at V = 65536) is allocated when the first guided
+        # request arrives; _guide_refs: id(task) -> (cache key, start row) of the admitted guided requests; _guided: the slots whose
+        # guide_state entry is not -1 (host mirror, like _bias_n)
+        self.guide_pool_rows = int(guide_pool_rows)
+        self._guides: Optional[GuidePool] = None
+        self._guide_refs: Dict[int, tuple] = {}
+        self._guided = [False] * batch_size
 
     # ------------------------------------------------------------------ set-up
     def _load_model(self):
@@ -428,9 +507,43 @@ class Worker:
         hi.copy_(ids, non_blocking=True)
         return (entries, hv, hi)
 
+    def _acquire_guides(self, task: Task) -> bool:
+        """References on the guides of `task` and of the choices that ride with it, taken at admission (a choice's guide must not be
+        dropped before the fork); builds a guide that is new.  On failure -- no room in the pool, a pattern the vocabulary cannot
+        realise -- nothing is held, `task` ends aborted with the reason in ``error`` (and an ("error", reason) message), and False
+        is returned: its siblings are ended by the caller."""
+        group = [t for t in [task] + task.siblings if t.guide is not None]
+        if not group:
+            return True
+        taken = []
+        try:
+            if self._guides is None:
+                self._guides = GuidePool(self.guide_pool_rows, self.real_state_size, self.model_config.vocab_size, self.device,
+                                         getattr(self.tokenizer, "idx2token", None))
+            for t in group:
+                taken.append((t, self._guides.acquire(t.guide, t.stop_tokens)))
+        except GuideError as exc:
+            for _, (key, _) in taken:
+                self._guides.release(key)
+            for t in [task] + task.siblings:
+                t.error = f"guided decoding: {exc}"
+            task.request_status = RequestStatus.FINISHED_ABORTED
+            task.output_queue.put_nowait(("error", task.error))
+            task.output_queue.put_nowait(("task_completed", task))
+            return False
+        for t, ref in taken:
+            self._guide_refs[id(t)] = ref
+        return True
+
+    def _release_guide(self, task: Task) -> None:
+        ref = self._guide_refs.pop(id(task), None)
+        if ref is not None:
+            self._guides.release(ref[0])
+
     def _process_accomplished_tasks(self, slots):
         for s in slots:
             t = self.state_slot[s]["task"]
+            self._release_guide(t)
             t.output_queue.put_nowait(("task_completed", t))
             self.state_slot[s] = _empty_slot()
 
@@ -452,6 +565,8 @@ class Worker:
                     break
                 continue
             self._install(task, slot)
+            if task.error is not None:                 # refused at admission (its guide): the next request is looked at in this step
+                prefills -= 1
 
     def _next_task(self) -> Optional[Task]:
         """The held group (nothing behind it is admitted first: FIFO), else the next task of the queue; None when there is none.  A
@@ -507,6 +622,7 @@ class Worker:
         t: Task = td["task"]
         t.request_status = RequestStatus.FINISHED_ABORTED
         t.output_queue.put_nowait(("task_completed", t))
+        self._release_guide(t)
         td["orphan"] = td["prefill_cached"] = True
         return True
 
@@ -580,6 +696,8 @@ class Worker:
             s0[:, :, [slot], :] = task.state[0].to(s0.device, non_blocking=True)
             s1[:, [slot], :, :] = task.state[1].to(s1.device, non_blocking=True)
             s2[[slot]] = task.state[2].to(s2.device, non_blocking=True)
+        if not self._acquire_guides(task):
+            return
         self._write_request_tables(task, slot)
         plp_prompt = list(task.prefill_tokens) if task.prompt_logprobs is not None else None
         if plp_prompt is not None and len(plp_prompt) == 1:      # its one position has no logprob: sent at once
@@ -628,6 +746,10 @@ class Worker:
                 self.bias_values[slot, :n_bias] = torch.tensor(list(task.logit_bias.values()), dtype=torch.float32)
             self.bias_counts[slot] = n_bias
             self._bias_n[slot] = n_bias
+        ref = self._guide_refs.get(id(task))
+        if ref is not None or self._guided[slot]:
+            self._guides.state[slot] = ref[1] if ref is not None else -1      # the guide's start row
+            self._guided[slot] = ref is not None
 
     def _organize_batch(self):
         """Slot ids per category, in slot order (the reference returns contiguous ranges after
@@ -671,6 +793,8 @@ class Worker:
             if seeded_rows:
                 ops.seeded_uniform(rows, idx, self.seeds, self.seeded, self.counters, u)
         lp_rows = [j for j, s in enumerate(decode_slots) if self.state_slot[s]["task"].logprobs]
+        g_rows = [j for j, s in enumerate(decode_slots) if self._guided[s]]
+        g_idx = self._slot_tensor(g_rows) if g_rows else None
         # single-token prefill rows that ask for prompt logprobs: their row list and targets, uploaded before the forward
         p_asks = [(nd + j, s) for j, s in enumerate(prefill_slots) if self.state_slot[s]["plp_prompt"] is not None]
         if p_asks:
@@ -721,6 +845,8 @@ class Worker:
         didx = idx[:nd]
         if any(self._bias_n[s] for s in decode_slots):     # after the forbidden tokens, before the penalties and every draw
             ops.apply_logit_bias(logits, didx, self.bias_counts, self.bias_ids, self.bias_values)
+        if g_rows:                                         # after the bias (a bias cannot re-admit a token), before the penalties
+            ops.guide_apply(logits, g_idx, didx, self._guides.state, self._guides.allow)
         # penalties for every decode row + arg-max, one kernel; occurrence is decayed in place
         status_out = None
         if self._commit_kernel is not None and self.device.type == "cuda":
@@ -747,6 +873,8 @@ class Worker:
                                                   self.top_k_tensor[srows[k]], u[k])
                 ids[lrows] = drawn.to(torch.int32)
         self._commit_sampled(ids, didx, status_out)
+        if g_rows:                                         # the sampled ids move the guided slots' states, on the device
+            ops.guide_advance(g_idx, didx, ids, self._guides.tok_off, self._guides.tok_bytes, self._guides.next, self._guides.state)
         lp = None
         if lp_rows:                                         # the sampled ids are read on the device, in place
             lp_val, lp_ids = ops.token_logprobs(snap, lp_k, targets=ids, target_rows=lp_idx)
@@ -951,4 +1079,4 @@ def model_load_config_for(model_path: str, vocab_path: str, vocab_size: int = 65
     return ModelLoadConfig(model_path=model_path, vocab_path=vocab_path, vocab_size=vocab_size, head_size=64)
 
 
-__all__ = ["Worker", "StateCategory", "min_swaps_to_target_fast", "types"]
+__all__ = ["Worker", "GuidePool", "StateCategory", "min_swaps_to_target_fast", "types"]

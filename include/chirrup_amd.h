@@ -521,6 +521,36 @@ int rwkv7_apply_logit_bias(int n_rows, int V, int cap, void *logits, const int32
                            const int32_t *ids, const float *values, void *stream);
 
 /*
+ * Guided decoding (chirrup_amd/guided.py, DESIGN.md "Guided decoding").  All guides of a worker share one pool of state rows:
+ * guide_next int32 [P][256] (entries are absolute pool rows, -1 = dead) and guide_allow uint32 [P][V/32] (bit t of a row: token t
+ * is allowed in that state).  A slot's constraint is guide_state[slot]: a pool row, or -1 for an unconstrained slot.  The token
+ * byte table is tok_off int32 [V + 1] (ascending offsets into tok_bytes; an id without a vocabulary entry has an empty range).
+ * A row index outside [0, P) met anywhere counts as dead / unconstrained.
+ *
+ * rwkv7_guide_build fills guide_allow rows [row0, row0 + S) (row0 + S <= P, S <= 65535, V % 64 == 0, guide_allow 8-byte aligned):
+ * bit (s, t) is set iff token t has bytes and walking them from row row0 + s through guide_next never meets a dead entry; for the
+ * n_special ids in `special` (the request's stop tokens) the bit is accept[s] != 0 instead (accept uint8 [S]) -- their bytes are
+ * not walked.  guide_next rows [row0, row0 + S) must already hold the guide (stream order).
+ *
+ * rwkv7_guide_apply: for i < n_rows, r = rows[i] (a row of binary16 logits [n_logit_rows][V], V % 32 == 0, 16-byte aligned),
+ * s = slot_idx[r] (or r), st = guide_state[s] (n_slots entries): when st >= 0, logits[r][t] = -inf for every t whose bit in
+ * guide_allow[st] is clear (NaN included); allowed entries and rows of unconstrained slots are not written.
+ *
+ * rwkv7_guide_advance: for i < n_rows, r = rows[i], s = slot_idx[r] (or r): when guide_state[s] >= 0 and ids[r] (n_ids entries)
+ * has bytes, guide_state[s] = the row after walking them; the state is left as it is when the walk dies (a stop id, a row that
+ * will be dropped) or the id is outside [0, V) or has no bytes.  A slot appears at most once among the rows.
+ *
+ * n_rows == 0 (S == 0) launches nothing.
+ */
+int rwkv7_guide_build(int S, int row0, int P, int V, const int32_t *guide_next, const int32_t *tok_off, const uint8_t *tok_bytes,
+                      int n_special, const int32_t *special, const uint8_t *accept, uint32_t *guide_allow, void *stream);
+int rwkv7_guide_apply(int n_rows, int n_logit_rows, int V, int P, void *logits, const int32_t *rows, const int32_t *slot_idx,
+                      int n_slots, const int32_t *guide_state, const uint32_t *guide_allow, void *stream);
+int rwkv7_guide_advance(int n_rows, int n_ids, int V, int P, const int32_t *rows, const int32_t *slot_idx, int n_slots,
+                        const int32_t *ids, const int32_t *tok_off, const uint8_t *tok_bytes, const int32_t *guide_next,
+                        int32_t *guide_state, void *stream);
+
+/*
  * The pieces of mm8t_seq for a decode step that folds the mm8 prologue / reduce launches into the neighbouring kernels
  * (chirrup_amd/rwkv7.py, ffn_dtype = int8): LN kernel (prologue of ffn.key, rwkv7_add_ln_mix_mm8) -> mm8t_gemm_partial ->
  * mm8_reduce_rows (corrections + relu^2 of ffn.key AND the prologue of ffn.value) -> mm8t_gemm_partial -> next LN kernel
