@@ -28,6 +28,7 @@ DEFAULT_SAMPLING_CONFIG: Dict[str, Any] = {
     "max_tokens": 8192,
 }
 LOGIT_BIAS_MAX = 1024          # entries of one request's logit_bias (the worker's per-slot list capacity)
+EMBED_POOLINGS = ("mean", "last")   # Task.embed
 GUIDE_MAX_STATES = 4096        # states of one guide's byte DFA (chirrup_amd/guided.py); a state is one row of the worker's guide pool
 
 
@@ -117,6 +118,13 @@ class Task:
     # leave the automaton; a stop token is allowed in accepting states only, so "stop" means the text matches (max_tokens may still
     # cut it short).  Needs stop tokens and max_tokens > 0; logprobs still measure the raw output (DESIGN.md "Guided decoding")
     guide: Any = None
+    # text embedding ("mean" | "last"; None: an ordinary request): the request only prefills -- every prompt token is fed, the last
+    # one too -- and answers ("embedding", {"embedding", "pooled_tokens", "prompt_tokens"}): the binary16 ln_out rows (what the head
+    # would multiply) of the prompt positions >= embed_skip, averaged or the last one, L2-normalised when embed_normalize.  Nothing
+    # is sampled, so the sampling fields are ignored (DESIGN.md "Embeddings")
+    embed: Optional[str] = None
+    embed_skip: int = 0
+    embed_normalize: bool = True
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -157,6 +165,18 @@ class Task:
             if self.max_tokens == 0 or self.prompt_logprobs is not None:
                 raise ValueError("a guide applies to generated tokens only: not with max_tokens=0 or prompt_logprobs")
         self.check_group()
+        if self.embed is not None:
+            if self.embed not in EMBED_POOLINGS:
+                raise ValueError(f"embed: unknown pooling {self.embed!r}, expected one of {', '.join(EMBED_POOLINGS)}")
+            self.embed_skip = _integer(self.embed_skip, "embed_skip")
+            for name, on in (("logprobs", self.logprobs), ("prompt_logprobs", self.prompt_logprobs is not None),
+                             ("return_logits", self.return_logits), ("guide", self.guide is not None),
+                             ("siblings", bool(self.siblings)), ("choice_index > 0", self.choice_index > 0),
+                             ("cache_prefill", self.cache_prefill), ("state", self.state is not None)):
+                if on:
+                    raise ValueError(f"embed cannot be combined with {name}")
+            if self.embed_skip < 0 or len(self.prefill_tokens) - self.embed_skip < 1:
+                raise ValueError(f"embed: no prompt position to pool ({len(self.prefill_tokens)} tokens, embed_skip {self.embed_skip})")
 
     def check_group(self) -> None:
         """Validates choice_index and siblings (at construction, and by whoever assembles a group afterwards)."""
@@ -167,6 +187,8 @@ class Task:
         for j, sib in enumerate(self.siblings, start=1):
             if not isinstance(sib, Task) or sib.siblings or sib.choice_index != j:
                 raise ValueError(f"sibling {j} must be a Task with choice_index {j} and no siblings of its own")
+        if any(getattr(t, "embed", None) is not None for t in [self] + self.siblings) and (self.siblings or self.choice_index > 0):
+            raise ValueError("embed cannot be combined with siblings / choice_index > 0")
         if self.siblings:
             if any(t.prompt_logprobs is not None for t in [self] + self.siblings):
                 raise ValueError("parallel choices (n > 1) cannot be combined with prompt_logprobs")

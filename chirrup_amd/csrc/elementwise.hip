@@ -734,3 +734,69 @@ extern "C" int rwkv7_fork_states(int n_groups, int L, int S, int C, int H, const
                        elapsed);
     return (int)hipGetLastError();
 }
+
+// Text embeddings: the ln_out rows of a prefill chunk pooled per sequence (include/chirrup_amd.h: rwkv7_pool_rows).  Grid (pieces of
+// a row, listed sequences); a lane owns 8 channels of one sequence and walks its tokens t0..T-1 IN ORDER: kPoolAhead 16-byte loads
+// are issued together, then added one after the other into eight binary32 sums -- the result depends on the token order only, not on
+// how the prompt was cut into chunks.  No atomics, no split over t.  The last row is kept as it was loaded (a copy of bits).
+// Bytes: every pooled row read once (B*T*C*2 when every sequence pools from t0 = 0), 6 * C bytes per sequence of accumulators.
+namespace {
+constexpr int kPoolThreads = 64, kPoolAhead = 16;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(kPoolThreads) void pool_rows_kernel(const int B, const int T, const int C, const int n_slots,
+                                                                 const f16 *__restrict__ xo, const int32_t *__restrict__ seq,
+                                                                 const int32_t *__restrict__ t0, const int32_t *__restrict__ slot,
+                                                                 float *__restrict__ acc_sum, f16 *__restrict__ acc_last,
+                                                                 int32_t *__restrict__ acc_count) {
+    const int i = blockIdx.y, b = seq[i], s = slot[i];
+    if (b < 0 || b >= B || s < 0 || s >= n_slots) return;
+    const int a = min(max(t0[i], 0), T);
+    if (a >= T) return;                                // nothing pooled: none of the three rows is written
+    const int chunk = blockIdx.x * kPoolThreads + threadIdx.x;
+    if (chunk == 0) acc_count[s] += T - a;
+    if (chunk >= (C >> 3)) return;
+    const f16x8 *src = reinterpret_cast<const f16x8 *>(xo + ((int64_t)b * T + a) * C) + chunk;
+    const int stride = C >> 3;                         // 16-byte vectors per row
+    f32x4 *sum = reinterpret_cast<f32x4 *>(acc_sum + (int64_t)s * C) + 2 * chunk;
+    f32x4 lo = sum[0], hi = sum[1];
+    f16x8 v[kPoolAhead], last = {};
+    int n = T - a;
+    for (; n >= kPoolAhead; n -= kPoolAhead, src += (int64_t)kPoolAhead * stride) {
+#pragma unroll
+        for (int k = 0; k < kPoolAhead; k++) v[k] = src[(int64_t)k * stride];
+#pragma unroll
+        for (int k = 0; k < kPoolAhead; k++) {
+            lo += f32x4{(float)v[k][0], (float)v[k][1], (float)v[k][2], (float)v[k][3]};
+            hi += f32x4{(float)v[k][4], (float)v[k][5], (float)v[k][6], (float)v[k][7]};
+        }
+        last = v[kPoolAhead - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < kPoolAhead - 1; k++)               // the remainder: its loads go out together too
+        if (k < n) v[k] = src[(int64_t)k * stride];
+#pragma unroll
+    for (int k = 0; k < kPoolAhead - 1; k++) {
+        if (k < n) {
+            lo += f32x4{(float)v[k][0], (float)v[k][1], (float)v[k][2], (float)v[k][3]};
+            hi += f32x4{(float)v[k][4], (float)v[k][5], (float)v[k][6], (float)v[k][7]};
+            last = v[k];
+        }
+    }
+    sum[0] = lo, sum[1] = hi;
+    reinterpret_cast<f16x8 *>(acc_last + (int64_t)s * C)[chunk] = last;
+}
+}  // namespace
+
+extern "C" int rwkv7_pool_rows(int n_seq, int B, int T, int C, const void *xo, const int32_t *seq, const int32_t *t0,
+                               const int32_t *slot, int n_slots, float *acc_sum, void *acc_last, int32_t *acc_count, void *stream) {
+    if (n_seq < 0) return CHIRRUP_E_SHAPE;
+    if (n_seq == 0) return 0;
+    if (n_seq > 65535 || B <= 0 || T <= 0 || C <= 0 || (C & 7) || n_slots <= 0) return CHIRRUP_E_SHAPE;
+    if (!xo || !seq || !t0 || !slot || !acc_sum || !acc_last || !acc_count) return CHIRRUP_E_NULL;
+    if (mis16(xo) || mis16(acc_sum) || mis16(acc_last) || (reinterpret_cast<uintptr_t>(acc_count) & 3)) return CHIRRUP_E_ALIGN;
+    const unsigned pieces = (unsigned)(((C >> 3) + kPoolThreads - 1) / kPoolThreads);
+    hipLaunchKernelGGL(pool_rows_kernel, dim3(pieces, (unsigned)n_seq), dim3(kPoolThreads), 0, static_cast<hipStream_t>(stream), B, T, C,
+                       n_slots, static_cast<const f16 *>(xo), seq, t0, slot, acc_sum, static_cast<f16 *>(acc_last), acc_count);
+    return (int)hipGetLastError();
+}

@@ -290,6 +290,50 @@ class AsyncEngineCore:
                                      return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
                                      logit_bias=logit_bias, prompt_logprobs=prompt_logprobs, guide=guide)
 
+    def embed(self, prompt_str: Optional[str] = None, prefill_tokens: Optional[List[int]] = None, pooling: str = "mean",
+              normalize: bool = True, pad_zero: bool = True, priority: int = 0) -> "asyncio.Future":
+        """The text embedding of a prompt (DESIGN.md "Embeddings"): an awaitable of {"embedding": float32 ndarray [C],
+        "pooled_tokens", "prompt_tokens"}.  The binary16 ln_out rows after each prompt token, averaged ("mean") or the last one
+        ("last"), L2-normalised unless normalize=False.  pad_zero feeds the token 0 in front, as the other routes do; that position
+        is left out of the pool.  The request only prefills and bypasses the prefix-state cache in both directions.  ValueError
+        for an empty prompt or an unknown pooling, RuntimeError when the request ends without a vector (abort, worker failure)."""
+        if not self.is_initialized:
+            raise RuntimeError("Engine not initialized")
+        if self.is_shutdown:
+            raise RuntimeError("Engine has been shutdown")
+        tokens = list(prefill_tokens) if prefill_tokens is not None else self.tokenizer.encode(prompt_str or "")
+        if not tokens:
+            raise ValueError("embed: the prompt is empty")
+        bad = [t for t in tokens if not 0 <= t < (self.vocab_size if self.vocab_size is not None else 1 << 62)]
+        if bad:
+            raise ValueError(f"embed: token id {bad[0]} is outside the vocabulary (size {self.vocab_size})")
+        task_id = str(uuid.uuid4())
+        abort_channel = None
+        if self.worker_mode == "process":
+            from .engine_process import AbortChannel
+
+            abort_channel = AbortChannel(task_id, [w.abort_q for w in self.workers])
+        skip = 1 if pad_zero else 0
+        completion = AsyncEngineCompletion(prompt_str=prompt_str or "", prefill_tokens=[0] * skip + tokens, state=None,
+                                           task_queue=self.task_queue, result_channel=ThreadSafeAsyncQueue(self.event_loop),
+                                           task_id=task_id, priority=priority, task_event_queue=abort_channel, max_tokens=0,
+                                           embed=pooling, embed_skip=skip, embed_normalize=bool(normalize))
+
+        async def run():
+            payload = None
+            try:
+                async for ev in completion:
+                    if ev[0] == "embedding":
+                        payload = ev[1]
+            except asyncio.CancelledError:
+                completion.abort()
+                raise
+            if payload is None:
+                raise RuntimeError(f"the embedding request ended without a vector ({completion.error or completion.task.request_status})")
+            return payload
+
+        return asyncio.ensure_future(run())
+
     def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
                       guided_json: Optional[Dict[str, Any]] = None):
         """The compiled guide completion() would use for these arguments (None without any); GuideError for a bad one.  A front end

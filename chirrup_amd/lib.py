@@ -69,6 +69,7 @@ SIGNATURES = {
     "rwkv7_advance_elapsed": (_i, [_i, _i, _vp, _vp, _vp]),
     "rwkv7_copy_slot_rows": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "rwkv7_fork_states": (_i, [_i, _i, _i, _i, _i] + [_vp] * 7),
+    "rwkv7_pool_rows": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "skinny_gemm_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "skinny_gemm_splits": (_i, [_i, _i, _i, _i]),
     "skinny_gemm_batched_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),

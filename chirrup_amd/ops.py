@@ -1474,6 +1474,53 @@ def _guide_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, guide_next, gui
             guide_state[s] = st
 
 
+def pool_rows(xo, seq, t0, slot, acc_sum, acc_last, acc_count) -> None:
+    """Pools the ln_out rows of a chunk per sequence for text embeddings (include/chirrup_amd.h: rwkv7_pool_rows): for i, with
+    b = seq[i], s = slot[i], a = t0[i]: acc_sum[s] += xo[b][a..T-1] in binary32, strictly in token order; acc_last[s] = xo[b][T-1]
+    (bits) when a < T; acc_count[s] += T - a.  xo fp16 [B, T, C]; seq / t0 / slot int32 [n]; acc_sum fp32 [n_slots, C], acc_last
+    fp16 [n_slots, C], acc_count int32 [n_slots], all in place.  CPU tensors take the numpy form: the same additions in the same
+    order, so the two agree bit for bit."""
+    if xo.dtype != torch.float16 or xo.dim() != 3 or not xo.is_contiguous():
+        raise _lib.ChirrupAmdError("xo: expected contiguous fp16 [B, T, C]")
+    B, T, C = xo.shape
+    n = seq.numel()
+    if any(t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n for t in (seq, t0, slot)):
+        raise _lib.ChirrupAmdError("seq / t0 / slot: expected int32 vectors of one length")
+    S = acc_count.numel()
+    if (acc_sum.dtype != torch.float32 or acc_last.dtype != torch.float16 or acc_count.dtype != torch.int32
+            or tuple(acc_sum.shape) != (S, C) or tuple(acc_last.shape) != (S, C) or acc_count.dim() != 1
+            or not (acc_sum.is_contiguous() and acc_last.is_contiguous() and acc_count.is_contiguous())):
+        raise _lib.ChirrupAmdError("acc_sum fp32 [n_slots, C], acc_last fp16 [n_slots, C], acc_count int32 [n_slots]: contiguous")
+    if n == 0:
+        return
+    if not xo.is_cuda:
+        _pool_rows_host(xo, seq, t0, slot, acc_sum, acc_last, acc_count)
+        return
+    for name, t in (("seq", seq), ("t0", t0), ("slot", slot), ("acc_sum", acc_sum), ("acc_last", acc_last), ("acc_count", acc_count)):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_pool_rows(n, B, T, C, _ptr(xo), _ptr(seq), _ptr(t0), _ptr(slot), S, _ptr(acc_sum), _ptr(acc_last),
+                                     _ptr(acc_count), _stream())
+    _lib.check(rc, "rwkv7_pool_rows")
+
+
+def _pool_rows_host(xo, seq, t0, slot, acc_sum, acc_last, acc_count):
+    import numpy as np
+
+    B, T, C = xo.shape
+    x, S = xo.numpy(), acc_count.numel()
+    sums, last, count = acc_sum.numpy(), acc_last.numpy(), acc_count.numpy()      # views: rows are written in place
+    for b, a, s in zip(seq.tolist(), t0.tolist(), slot.tolist()):
+        a = min(max(a, 0), T)
+        if not 0 <= b < B or not 0 <= s < S or a >= T:
+            continue
+        acc = sums[s].copy()
+        for t in range(a, T):                               # one binary32 addition per channel and token, in token order
+            acc = acc + x[b, t].astype(np.float32)
+        sums[s] = acc
+        last[s].view(np.uint16)[:] = x[b, T - 1].view(np.uint16)
+        count[s] += T - a
+
+
 def lora_act_(hbuf, first_plane: int) -> None:
     """hbuf [n, rows, D] fp16, planes first_plane.. of [v, w, a, g]: tanh on w, sigmoid on g."""
     _chk16("hbuf", hbuf)

@@ -652,14 +652,17 @@ class RWKV_x070:
         return F.linear(x, z["head.weight"])
 
     def forward_slots(self, idxs, pool, slot_idx: torch.Tensor, full_output: bool = False, feedback=None, zero_sync: bool = False,
-                      logit_rows: Optional[torch.Tensor] = None, row_sink: Optional[Callable] = None):
+                      logit_rows: Optional[torch.Tensor] = None, row_sink: Optional[Callable] = None, pool_rows=None):
         """State-pool form of forward_seq_batch_seperate (not in the reference): ``pool`` is the
         worker's WHOLE slot table [fp16[L,2,n,C], fp16[L,n,H,64,64], int32[n]] and batch row b lives
         in slot ``slot_idx[b]`` (int32 [B] on the device, all distinct).  Nothing is gathered or
         swapped: the kernels address the slot tables directly (SURVEY.md section 8f "next 1").
         logit_rows: int32 [R] on the device, ascending flattened token rows b*T + t: the call then returns (logits, head output of
         those rows, fp16 [R, V]) -- or, with row_sink, calls row_sink(r0, block) for consecutive blocks of at most
-        HEAD_ROWS_BLOCK rows in order and returns (logits, None), so that a chunk's rows never exist all at once (prompt logprobs)."""
+        HEAD_ROWS_BLOCK rows in order and returns (logits, None), so that a chunk's rows never exist all at once (prompt logprobs).
+        pool_rows: (seq, t0, slot, acc_sum, acc_last, acc_count) of ops.pool_rows -- the ln_out rows t0[i]..T-1 of batch row seq[i]
+        are pooled into row slot[i] of the three accumulator tables by one launch (text embeddings); the returned logits and the
+        state are those of the same call without it.  May be combined with logit_rows (the return is then the pair above)."""
         if not self.fused:
             raise ops._lib.ChirrupAmdError("forward_slots needs the fused HIP path (a GPU)")
         if isinstance(idxs, torch.Tensor):
@@ -670,14 +673,17 @@ class RWKV_x070:
         # one launch: the embedding rows (a negative token takes feedback[its slot], the id the sampler left there), the slots'
         # step counters in row order and, for a decode graph, the zeroing of the stream's launch-sync words
         x, elapsed_rows = ops.embed_rows(self.z["emb.weight"], tok.contiguous(), slot_idx, feedback, zero_sync, elapsed_pool=pool[2])
-        if logit_rows is None:
+        if logit_rows is None and pool_rows is None:
             return self._forward_embedded_fused(x, pool, tok.shape[1], full_output, slot_idx=slot_idx, elapsed_rows=elapsed_rows)
         if full_output:
-            raise ValueError("logit_rows and full_output are exclusive")
-        if logit_rows.dtype != torch.int32 or logit_rows.dim() != 1 or logit_rows.device != self.device:
+            raise ValueError("logit_rows / pool_rows and full_output are exclusive")
+        if logit_rows is not None and (logit_rows.dtype != torch.int32 or logit_rows.dim() != 1 or logit_rows.device != self.device):
             raise ops._lib.ChirrupAmdError("logit_rows: expected int32 [R] on the model's device")
-        return self._forward_embedded_fused(x, pool, tok.shape[1], False, slot_idx=slot_idx, elapsed_rows=elapsed_rows,
-                                            logit_rows=(logit_rows, row_sink))
+        if pool_rows is not None and len(pool_rows) != 6:
+            raise ValueError("pool_rows: expected (seq, t0, slot, acc_sum, acc_last, acc_count)")
+        out = self._forward_embedded_fused(x, pool, tok.shape[1], False, slot_idx=slot_idx, elapsed_rows=elapsed_rows,
+                                           logit_rows=(logit_rows, row_sink, pool_rows))
+        return out if logit_rows is not None else out[0]
 
     def _forward_embedded_fused(self, x, state, T, full_output, slot_idx=None, elapsed_rows=None, logit_rows=None):
         """_forward_embedded's arithmetic as plan_forward dispatches it: every element-wise chain in one HIP kernel (csrc/elementwise.hip,
@@ -699,6 +705,9 @@ class RWKV_x070:
             self._tmix_core(p, f, i, lw, rkv, up, s1[i])
             self._att_output(p, f, lw, s0[i][1], w_O)
             self._channel_mix(p, f, lw, w_fK, w_fV)
+        if logit_rows is not None and logit_rows[0] is None:      # pool_rows alone: the plain exit's logits, bit for bit
+            self._ln_out_pool(f, logit_rows[2])
+            return self._ln_out_head(p, f, False, s2), None
         if logit_rows is not None:
             return self._ln_out_rows(p, f, s2, *logit_rows)
         return self._ln_out_head(p, f, full_output, s2)
@@ -943,16 +952,29 @@ class RWKV_x070:
             return parts[0] if len(parts) == 1 else torch.cat(parts)
         return F.linear(x2, self.z["head.weight"])
 
-    def _ln_out_rows(self, p: _Plan, f, s2, rows: torch.Tensor, row_sink):
+    def _ln_out_pool(self, f, pool):
+        """Text embeddings: ln_out over ALL B*T rows (the full_output route: one add_ln_mix, nothing of f is changed), pooled per
+        sequence by one ops.pool_rows launch.  The caller then takes _ln_out_head as it stands, so the logits of a pooling forward
+        are those of the plain one whatever the plan (its T > 1 form sums split-K partials on its own, in its own order)."""
+        z, B, T, C = self.z, f.B, f.T, f.C
+        xo = f.new(B, T, C)
+        ops.add_ln_mix(B, T, C, f.x, f.delta, None, z["ln_out.weight"], z["ln_out.bias"], 1e-5, None, None,
+                       None, xo, delta_partials=f.dparts, mm8_in=f.dq)
+        ops.pool_rows(xo, *pool)
+
+    def _ln_out_rows(self, p: _Plan, f, s2, rows: torch.Tensor, row_sink, pool=None):
         """_ln_out_head for a forward that also wants the head output of chosen token rows: ln_out over ALL B*T rows (the
         full_output route: one add_ln_mix), then the last token of each sequence through the plan's head -- the returned logits --
-        and the chosen rows gathered and through _head_rows, HEAD_ROWS_BLOCK rows at a time."""
+        and the chosen rows gathered and through _head_rows, HEAD_ROWS_BLOCK rows at a time.  pool: the ops.pool_rows arguments
+        behind xo -- the rows are pooled per sequence (text embeddings), one launch, before the head reads them."""
         z, B, T, C = self.z, f.B, f.T, f.C
         xo = f.new(B, T, C)
         ops.add_ln_mix(B, T, C, f.x, f.delta, None, z["ln_out.weight"], z["ln_out.bias"], 1e-5, None, None,
                        None, xo, delta_partials=f.dparts, mm8_in=f.dq)
         if f.slot_idx is not None:
             ops.advance_elapsed(s2, T, f.slot_idx)
+        if pool is not None:
+            ops.pool_rows(xo, *pool)
         last = xo[:, -1, :].contiguous()
         if p.head == "mm8":
             out = ops.mm8t_linear(last, *self.head8, tiled=self._head8_tiled)

@@ -6,26 +6,30 @@ prefix-state cache protocol (`check_and_wait_prefill` -> `completion(state=...)`
 ("cache_prefill", ...) event; in process mode the states are arena row addresses and never leave HBM) and 10-s keep-alive comments.
 `POST /v1/completions` is OpenAI's legacy text route (not in the reference): raw prompts, and with `echo` + `logprobs` the scores of
 the prompt's own tokens (prompt logprobs, `max_tokens=0` to score only) -- what evaluation harnesses call.
+`POST /v1/embeddings` is OpenAI's embeddings route (not in the reference either): one vector per input, the pooled hidden state in
+front of the head (DESIGN.md "Embeddings").
 Not here: the settings CLI and the batch translate / rollout routes (out of scope).
 
     app = create_app(engine, state_cache_size=50)       # engine: an initialised AsyncEngineCore
 """
 import asyncio
+import base64
 import json
 import re
 import time
 import uuid
-from typing import Any, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, List, Literal, Optional, Tuple, Union
 
 from fastapi import FastAPI, HTTPException
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, model_validator
 
-from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, LOGIT_BIAS_MAX, RequestStatus
+from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, EMBED_POOLINGS, LOGIT_BIAS_MAX, RequestStatus
 from .guided import GuideError
 from .state_cache import SimpleStateCache
 
 KEEP_ALIVE_S = 10.0
+EMBEDDING_INPUTS_MAX = 2048      # inputs of one /v1/embeddings request (OpenAI's limit)
 _SSE_HEADERS = {"Cache-Control": "no-cache", "Connection": "keep-alive", "X-Accel-Buffering": "no"}
 
 
@@ -170,6 +174,26 @@ class CompletionRequest(BaseModel):
 
     def token_bias(self) -> Dict[int, float]:
         return {int(k): float(v) for k, v in (self.logit_bias or {}).items()}
+
+
+class EmbeddingRequest(BaseModel):
+    """OpenAI's embeddings request.  input: a string, a list of strings, one tokenised input (a list of token ids) or a list of
+    those; encoding_format "base64": the vector as little-endian float32 bytes.  Extension fields: pooling ("mean" | "last" of the
+    hidden states), normalize (L2), pad_zero (the token 0 in front, as on the other routes; it is not pooled).  dimensions is refused:
+    these are a language model's hidden states, and a truncated one means nothing."""
+    model: str = "rwkv-latest"
+    input: Union[str, List[int], List[str], List[List[int]]]
+    encoding_format: Literal["float", "base64"] = "float"
+    dimensions: Optional[int] = None
+    pooling: str = "mean"
+    normalize: bool = True
+    pad_zero: bool = True
+
+    def inputs(self) -> List[Union[str, List[int]]]:
+        p = self.input
+        if isinstance(p, str) or (p and all(isinstance(x, int) for x in p)):
+            return [p]
+        return list(p)
 
 
 def legacy_top(idx2token: Dict[int, bytes], top) -> Optional[Dict[str, float]]:
@@ -557,7 +581,61 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
 
         return StreamingResponse(body(), media_type="text/event-stream" if request.stream else "application/json", headers=_SSE_HEADERS)
 
+    @app.post("/v1/embeddings")
+    async def embeddings(request: EmbeddingRequest):
+        if not engine.is_initialized or engine.is_shutdown:
+            raise HTTPException(status_code=503, detail="model not loaded")
+        if request.dimensions is not None:
+            raise HTTPException(status_code=400, detail="dimensions is not supported: the vectors are hidden states of a language "
+                                "model, and a truncated one means nothing")
+        if request.pooling not in EMBED_POOLINGS:
+            raise HTTPException(status_code=400, detail=f"pooling: expected one of {', '.join(EMBED_POOLINGS)}")
+        items = request.inputs()
+        if not items:
+            raise HTTPException(status_code=400, detail="input is empty")
+        if len(items) > EMBEDDING_INPUTS_MAX:
+            raise HTTPException(status_code=400, detail=f"input holds {len(items)} entries, at most {EMBEDDING_INPUTS_MAX} are allowed")
+        vocab = getattr(engine, "vocab_size", None)
+        token_lists = []
+        for i, p in enumerate(items):
+            try:
+                ids = engine.tokenizer.encode(p) if isinstance(p, str) else list(p)
+            except Exception as e:                              # noqa: BLE001
+                raise HTTPException(status_code=500, detail=f"embedding failed: {e}")
+            if not ids:
+                raise HTTPException(status_code=400, detail=f"input {i} is empty")
+            if any(not 0 <= t < (vocab if vocab is not None else 1 << 62) for t in ids):
+                raise HTTPException(status_code=400, detail=f"input {i}: a token id is outside the vocabulary")
+            token_lists.append(ids)
+        try:                                                    # one engine request per input, spread over all workers
+            futures = [engine.embed(prefill_tokens=ids, pooling=request.pooling, normalize=request.normalize, pad_zero=request.pad_zero)
+                       for ids in token_lists]
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        except RuntimeError as e:
+            raise HTTPException(status_code=503, detail=str(e))
+        try:
+            results = await asyncio.gather(*futures)
+        except Exception as e:                                  # noqa: BLE001
+            for f in futures:
+                f.cancel()
+            raise HTTPException(status_code=500, detail=f"embedding failed: {e}")
+        except asyncio.CancelledError:                          # client gone: stop prefilling
+            for f in futures:
+                f.cancel()
+            raise
+
+        def encoded(vec):
+            if request.encoding_format == "base64":
+                return base64.b64encode(vec.astype("<f4").tobytes()).decode("ascii")
+            return [float(v) for v in vec]
+
+        n_in = sum(int(r["prompt_tokens"]) for r in results)
+        return {"object": "list", "data": [{"object": "embedding", "index": i, "embedding": encoded(r["embedding"])}
+                                           for i, r in enumerate(results)],
+                "model": request.model, "usage": {"prompt_tokens": n_in, "total_tokens": n_in}}
+
     return app
 
 
-__all__ = ["create_app", "ChatCompletionRequest", "ChatMessage", "CompletionRequest", "ThinkSplitter", "chat_prompt"]
+__all__ = ["create_app", "ChatCompletionRequest", "ChatMessage", "CompletionRequest", "EmbeddingRequest", "ThinkSplitter", "chat_prompt"]

@@ -42,6 +42,7 @@ import torch
 
 from . import ops
 from .core_structure import LOGIT_BIAS_MAX, ModelLoadConfig, RequestStatus, Task
+from .embeddings import finish as finish_embedding
 from .guided import GuideError, token_table
 from .samplers import is_greedy_row, sample_inverse_cdf, sample_logits_rwkv_pip_compatible
 
@@ -79,8 +80,8 @@ def _empty_slot() -> dict:
     # feedback: the slot's next decode input is last_ids[slot] on the device.  Prompt logprobs (task.prompt_logprobs set):
     # plp_prompt = the tokens as admitted, plp_next = index of the next one to feed, plp_sent = positions already sent.
     # Parallel choices: siblings = [(slot, task)] of the choices waiting suspended for this slot's prefill (until the fork); orphan:
-    # choice 0 has aborted and the slot prefills on for its live siblings only
-    return {"task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
+    # choice 0 has aborted and the slot prefills on for its live siblings only.  emb_fed: prompt positions an embedding request has fed
+    return {"emb_fed": 0, "task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
             "state_category": StateCategory.EMPTY, "prefilled_tokens": [], "prefill_cached": False,
             "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0, "siblings": None, "orphan": False}
 
@@ -209,6 +210,12 @@ class Worker:
         self._guides: Optional[GuidePool] = None
         self._guide_refs: Dict[int, tuple] = {}
         self._guided = [False] * batch_size
+        # text embeddings (DESIGN.md "Embeddings"): per-slot accumulators (sum fp32 [n, C], last row fp16 [n, C], rows int32 [n]) that
+        # ops.pool_rows fills chunk by chunk, allocated when the first embedding request arrives; _emb_host: two sets of pinned host
+        # copies (the loop runs one forward ahead of the host), _emb_downloads picks the set
+        self._emb = None
+        self._emb_host = None
+        self._emb_downloads = 0
 
     # ------------------------------------------------------------------ set-up
     def _load_model(self):
@@ -333,6 +340,8 @@ class Worker:
 
     def _handle_forward_seq(self, td, slot: int):
         t: Task = td["task"]
+        if t.embed is not None:                         # an embedding is prefilled by chunks only, whatever is left of it
+            return
         if self._maybe_cache_prefill(td, slot):
             td["state_category"] = StateCategory.FORWARD_ONE_PREFILL
         if len(t.prefill_tokens) == 0:
@@ -419,6 +428,8 @@ class Worker:
             rec["event"].synchronize()
         if rec.get("plp") is not None:
             self._handle_prompt_logprobs(rec["plp"])
+        if rec.get("emb") is not None:
+            self._handle_embeddings(*rec["emb"])
         n_rows = len(rec["rows"])
         if n_rows == 0:
             return
@@ -469,6 +480,39 @@ class Worker:
                 task.request_status = RequestStatus.FINISHED_LENGTH_CAPPED
                 done.append(slot)
         self._process_accomplished_tasks(done)
+
+    def _handle_embeddings(self, entries, sums, lasts, counts):
+        """Finish the embeddings whose last chunk one step ran: entries (slot, task, tokens fed); sums / lasts / counts: host copies
+        of the accumulator tables' rows of those slots.  A request that has ended meanwhile (abort) is dropped."""
+        done = []
+        for slot, task, fed in entries:
+            td = self.state_slot[slot]
+            if td["task"] is not task or RequestStatus.is_finished(task.request_status):
+                continue
+            count = int(counts[slot])
+            vec = finish_embedding(sums[slot].numpy(), lasts[slot].numpy(), count, task.embed, task.embed_normalize)
+            task.output_queue.put_nowait(("embedding", {"embedding": vec, "pooled_tokens": count, "prompt_tokens": fed}))
+            task.request_status = RequestStatus.FINISHED_LENGTH_CAPPED
+            done.append(slot)
+        self._process_accomplished_tasks(done)
+
+    def _download_embeddings(self, entries):
+        """The record of the embeddings that fed their last token in this step: their slots' accumulator rows copied to pinned host
+        memory behind an event.  Two sets of host tables, used in turn: with run-ahead the previous set is read after this step's
+        forwards have been enqueued."""
+        self._emb_downloads += 1
+        if self.device.type != "cuda":
+            host = tuple(t.clone() for t in self._emb)
+            return {"rows": [], "ids": None, "event": None, "raw": {}, "status": False, "emb": (entries, *host)}
+        if self._emb_host is None:
+            self._emb_host = [tuple(torch.zeros(t.shape, dtype=t.dtype).pin_memory() for t in self._emb) for _ in range(2)]
+        host = self._emb_host[self._emb_downloads & 1]
+        for slot, _, _ in entries:
+            for h, d in zip(host, self._emb):
+                h[slot].copy_(d[slot], non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        return {"rows": [], "ids": None, "event": event, "raw": {}, "status": False, "emb": (entries, *host)}
 
     def _prompt_rows(self, asks, T: int):
         """Flattened rows b*T + t and their targets (the next prompt token) for the asking batch rows `asks` = [(b, slot)] of a
@@ -708,7 +752,10 @@ class Worker:
                 task.output_queue.put_nowait(("task_completed", task))
                 return
         first = task.prefill_tokens.pop(0)
-        if len(task.prefill_tokens) == 0:
+        if task.embed is not None:                      # chunks only (every token is fed, the last one too): never a single-token row
+            self._reset_embedding(slot)
+            cat, prefilling = StateCategory.FORWARD_SEQ, True
+        elif len(task.prefill_tokens) == 0:
             cat, prefilling = StateCategory.FORWARD_ONE_DECODE, False
         elif len(task.prefill_tokens) - max(task.cache_prefill_padding - 1, 0) < self.min_forward_seq_len:
             cat, prefilling = StateCategory.FORWARD_ONE_PREFILL, True
@@ -718,6 +765,16 @@ class Worker:
         td.update(task=task, is_prefilling=prefilling, next_input_token=first, state_category=cat, plp_prompt=plp_prompt,
                   plp_sent=1 if plp_prompt is not None and len(plp_prompt) == 1 else 0)
         self.state_slot[slot] = td
+
+    def _reset_embedding(self, slot: int):
+        """The slot's embedding accumulators, zeroed at admission (allocated on the first embedding request).  Stream-ordered writes:
+        the copies of the slot's previous embedding to the host were enqueued before them."""
+        if self._emb is None:
+            n, C, dev = self.real_state_size, int(self.batch_state[0].shape[3]), self.device
+            self._emb = (torch.zeros((n, C), dtype=torch.float32, device=dev), torch.zeros((n, C), dtype=torch.float16, device=dev),
+                         torch.zeros((n,), dtype=torch.int32, device=dev))
+        for t in self._emb:
+            t[slot].zero_()
 
     def _write_request_tables(self, task: Task, slot: int):
         """The slot's penalty, sampling, seed and bias tables for `task` (at admission; a sibling choice's at the fork)."""
@@ -920,26 +977,66 @@ class Worker:
                                                   feedback=self.last_ids)
         return g
 
+    def _seq_left(self, s: int) -> int:
+        """Tokens the chunk path may still feed for slot s: everything but the last prompt token (a single-token row feeds it) and
+        the cache padding -- for an embedding request every token that is left."""
+        td = self.state_slot[s]
+        t: Task = td["task"]
+        if t.embed is not None:
+            return 1 + len(t.prefill_tokens)
+        return len(t.prefill_tokens) - max(t.cache_prefill_padding - 1, 0)
+
     def _run_forward_seq(self, seq_slots: List[int]):
-        lens = [len(self.state_slot[s]["task"].prefill_tokens) - max(self.state_slot[s]["task"].cache_prefill_padding - 1, 0)
-                for s in seq_slots]
+        """The chunk forward(s) of a step.  Without an embedding request among the slots: one forward, as ever.  An embedding is fed
+        to its very last token by chunks, so what is left of one can be shorter than min_forward_seq_len, the least any other
+        sequence brings -- and one forward feeds every sequence the same number of tokens.  Rule: the embedding slots with fewer
+        than min_forward_seq_len tokens left run in a forward of their own, behind the others'; nobody's chunk gets shorter than it
+        would have been without them."""
+        if not any(self.state_slot[s]["task"].embed is not None for s in seq_slots):
+            return self._run_chunk(seq_slots, None)
+        short = [s for s in seq_slots if self.state_slot[s]["task"].embed is not None and self._seq_left(s) < self.min_forward_seq_len]
+        recs, finishing = [], []
+        for group in ([s for s in seq_slots if s not in short], short):
+            if group:
+                rec = self._run_chunk(group, finishing)
+                if rec is not None:
+                    recs.append(rec)
+        if finishing:
+            recs.append(self._download_embeddings(finishing))
+        return recs or None
+
+    def _run_chunk(self, seq_slots: List[int], finishing):
+        """One chunk forward of these slots; finishing collects (slot, task, tokens fed) of the embeddings that fed their last token."""
+        lens = [self._seq_left(s) for s in seq_slots]
         n_tok = min(self.max_forward_seq_len_per_forward, *lens)
         assert n_tok > 0
         asks = [(b, s) for b, s in enumerate(seq_slots) if self.state_slot[s]["plp_prompt"] is not None]
         if asks:                                            # (before the cursors below move)
             k = max(self.state_slot[s]["task"].prompt_logprobs for _, s in asks)
             rows, targets, entries = self._prompt_rows(asks, n_tok)
-        batch = []
-        for s in seq_slots:
+        batch, pools = [], []
+        for b, s in enumerate(seq_slots):
             td = self.state_slot[s]
             t: Task = td["task"]
             chunk = [td["next_input_token"]] + t.prefill_tokens[: n_tok - 1]
             td["prefilled_tokens"].extend(chunk)
             t.prefill_tokens = t.prefill_tokens[n_tok - 1:]
-            td["next_input_token"] = t.prefill_tokens.pop(0)
+            if t.embed is not None:
+                # (batch row, first pooled position of the chunk, slot): the leading embed_skip prompt positions are left out
+                pools.append((b, min(max(t.embed_skip - td["emb_fed"], 0), n_tok), s))
+                td["emb_fed"] += n_tok
+                td["next_input_token"] = t.prefill_tokens.pop(0) if t.prefill_tokens else None
+                if td["next_input_token"] is None:      # its last token is in this chunk: it waits for the pooled rows, then ends
+                    td["state_category"], td["is_prefilling"] = StateCategory.FORWARD_ONE_SUSPENDED, False
+                    finishing.append((s, t, td["emb_fed"]))
+            else:
+                td["next_input_token"] = t.prefill_tokens.pop(0)
             batch.append(chunk)
+        kw = {}
+        if pools:                                           # (only then: a backend without embeddings never sees the keyword)
+            kw["pool_rows"] = (*self._upload_int32(*[list(col) for col in zip(*pools)]), *self._emb)
         if not asks:
-            self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots))   # logits discarded (:776)
+            self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots), **kw)   # logits discarded (:776)
             return None
         # prompt logprobs: the head output of every row of the asking sequences, a block at a time, straight into the logprob
         # kernel (the target of row (b, t) is the prompt token after it); the results reach the host behind an event like the ids
@@ -952,7 +1049,7 @@ class Worker:
             lp[r0:r0 + block.shape[0]].copy_(v)
             ids[r0:r0 + block.shape[0]].copy_(i)
 
-        self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots), logit_rows=rows_dev, row_sink=sink)
+        self.model.forward_slots(batch, self.batch_state, self._slot_tensor(seq_slots), logit_rows=rows_dev, row_sink=sink, **kw)
         event = None
         plp = self._download_plp(entries, lp, ids)
         if self.device.type == "cuda":

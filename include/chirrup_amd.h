@@ -474,6 +474,20 @@ int rwkv7_copy_slot_rows(int B, int C, const int32_t *slot_idx, const void *src,
  * nothing.  Bytes per group: one slot's state read once, written once per destination. */
 int rwkv7_fork_states(int n_groups, int L, int S, int C, int H, const int32_t *src, const int32_t *dst_offs, const int32_t *dst,
                       void *shift, void *wkv, int32_t *elapsed, void *stream);
+/* Text embeddings: pools the ln_out rows of a prefill chunk per sequence.  xo binary16 [B][T][C] (the rows the head would multiply);
+ * for i < n_seq with b = seq[i], s = slot[i], a = t0[i] in [0, T] (clamped to it):
+ *   acc_sum[s][c]  continues its running binary32 sum over t = a..T-1 STRICTLY in token order, one channel at a time:
+ *                  sum = sum + (float)xo[b][t][c], no contraction -- so a sum depends on the rows and their order only, not on how a
+ *                  prompt was cut into chunks (the same rows pooled in one launch or in several give the same bits);
+ *   acc_last[s]    = xo[b][T-1], copied as bits, when a < T;
+ *   acc_count[s]  += T - a.
+ * acc_sum float [n_slots][C], acc_last binary16 [n_slots][C], acc_count int32 [n_slots]; rows of the three tables that are not listed
+ * (and those of a sequence with a == T) are not written.  Slots must be distinct; a b outside [0, B) or an s outside [0, n_slots) is
+ * skipped.  ONE launch: parallel over channels and sequences only, no floating-point atomics, no split over t (loads are issued
+ * ahead, the additions stay in order).  n_seq == 0 launches nothing.  C % 8 == 0; xo, acc_sum and acc_last 16-byte aligned.
+ * Bytes: each pooled row read once (B*T*C*2 at most) + 6*C bytes of accumulators read and written per listed sequence. */
+int rwkv7_pool_rows(int n_seq, int B, int T, int C, const void *xo, const int32_t *seq, const int32_t *t0, const int32_t *slot, int n_slots,
+                    float *acc_sum, void *acc_last, int32_t *acc_count, void *stream);
 
 /*
  * Sort-free top-p / top-k / temperature sampling of n_rows rows of `logits` (binary16 [B][V], V <= 65536,
