@@ -29,6 +29,8 @@ DEFAULT_SAMPLING_CONFIG: Dict[str, Any] = {
 }
 LOGIT_BIAS_MAX = 1024          # entries of one request's logit_bias (the worker's per-slot list capacity)
 EMBED_POOLINGS = ("mean", "last")   # Task.embed
+BEAM_WIDTH_MAX = 8             # Task.beam_width
+BEAM_K_MAX = 20                # candidates per beam and step, beam_width + len(stop_tokens): the top-K of the log-prob kernel (ops.TOP_LOGPROBS_MAX)
 GUIDE_MAX_STATES = 4096        # states of one guide's byte DFA (chirrup_amd/guided.py); a state is one row of the worker's guide pool
 
 
@@ -67,7 +69,7 @@ class RequestStatus(enum.IntEnum):
 class Task:
     """One generation request.  ``output_queue`` receives ("token_generated", (id, text[, logits])) -- (id, text, logits or None,
     logprobs) when ``logprobs`` is set --
-    ("cache_prefill", {"state", "prefilled_tokens"}) and ("task_completed", task) tuples;
+    ("cache_prefill", {"state", "prefilled_tokens"}), ("beams", {...}) (beam search) and ("task_completed", task) tuples;
     ``task_event_queue`` carries ("abort", payload) from the front end."""
 
     output_queue: Any
@@ -125,6 +127,14 @@ class Task:
     embed: Optional[str] = None
     embed_skip: int = 0
     embed_normalize: bool = True
+    # beam search (0: off; a width W in 2..BEAM_WIDTH_MAX): the request holds W slots and answers ONE ("beams", {"hypotheses",
+    # "prompt_tokens"}) message (prompt_tokens: the tokens fed -- behind a prefix-cache hit, the uncached remainder) with its
+    # beam_n_best (1..W) best hypotheses, ranked by cumulative_logprob / max(T, 1)**length_penalty (T text tokens), each {"token_ids", "text", "cumulative_logprob", "score", "finish_reason"}; nothing streams.  It needs
+    # 1 <= len(stop_tokens) <= BEAM_K_MAX - W and max_tokens > 0.  The search reads the raw model output: temperature, top_p, top_k,
+    # seed and the penalty fields are accepted and ignored (DESIGN.md "Beam search")
+    beam_width: int = 0
+    length_penalty: float = 1.0
+    beam_n_best: int = 1
 
     event_list: List = field(init=False, default_factory=list)
     request_status: RequestStatus = field(init=False, default=RequestStatus.WAITING)
@@ -165,6 +175,7 @@ class Task:
             if self.max_tokens == 0 or self.prompt_logprobs is not None:
                 raise ValueError("a guide applies to generated tokens only: not with max_tokens=0 or prompt_logprobs")
         self.check_group()
+        self.check_beam()
         if self.embed is not None:
             if self.embed not in EMBED_POOLINGS:
                 raise ValueError(f"embed: unknown pooling {self.embed!r}, expected one of {', '.join(EMBED_POOLINGS)}")
@@ -194,6 +205,36 @@ class Task:
                 raise ValueError("parallel choices (n > 1) cannot be combined with prompt_logprobs")
             if any(t.max_tokens == 0 for t in [self] + self.siblings):
                 raise ValueError("parallel choices (n > 1) need max_tokens > 0")
+
+    def check_beam(self) -> None:
+        """Validates the beam-search fields and what a beam request cannot be combined with (at construction)."""
+        self.beam_width = _integer(self.beam_width, "beam_width")
+        self.beam_n_best = _integer(self.beam_n_best, "beam_n_best")
+        lam = self.length_penalty
+        if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not math.isfinite(lam):
+            raise ValueError(f"length_penalty must be a finite number, got {lam!r}")
+        self.length_penalty = float(lam)
+        if self.beam_width == 0:
+            if self.beam_n_best != 1:
+                raise ValueError("beam_n_best needs beam_width")
+            return
+        W = self.beam_width
+        if not 2 <= W <= BEAM_WIDTH_MAX:
+            raise ValueError(f"beam_width must be 0 (off) or in 2..{BEAM_WIDTH_MAX}, got {W}")
+        if not 1 <= self.beam_n_best <= W:
+            raise ValueError(f"beam_n_best must be in 1..beam_width ({W}), got {self.beam_n_best}")
+        stops = set(self.stop_tokens or [])
+        if not 1 <= len(stops) <= BEAM_K_MAX - W:
+            raise ValueError(f"beam search needs 1..{BEAM_K_MAX - W} distinct stop tokens at beam_width {W}, got {len(stops)}")
+        if self.max_tokens is None or self.max_tokens == 0:
+            raise ValueError("beam search needs max_tokens > 0")
+        for name, on in (("logprobs", self.logprobs), ("return_logits", self.return_logits),
+                         ("prompt_logprobs", self.prompt_logprobs is not None), ("guide", self.guide is not None),
+                         ("logit_bias", bool(self.logit_bias)), ("forbidden_tokens", bool(self.forbidden_tokens)),
+                         ("embed", self.embed is not None), ("siblings", bool(self.siblings)),
+                         ("choice_index > 0", self.choice_index > 0)):
+            if on:
+                raise ValueError(f"beam search cannot be combined with {name}")
 
     def is_finished(self) -> bool:
         return RequestStatus.is_finished(self.request_status)

@@ -259,8 +259,14 @@ class AsyncEngineCore:
                    return_logits: bool = False, logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
                    logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None,
                    guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
-                   guided_json: Optional[Dict[str, Any]] = None) -> AsyncEngineCompletion:
-        """guided_regex / guided_choice / guided_json (at most one): the generated text must match the pattern, be one of the strings,
+                   guided_json: Optional[Dict[str, Any]] = None, beam_width: int = 0, length_penalty: float = 1.0,
+                   beam_n_best: int = 1) -> AsyncEngineCompletion:
+        """beam_width (2..8; 0: off): beam search (DESIGN.md "Beam search") -- the request holds beam_width slots of one worker,
+        streams nothing and yields one ("beams", {"hypotheses", "prompt_tokens"}) event with its beam_n_best best hypotheses, ranked by
+        cumulative_logprob / max(T, 1) ** length_penalty.  It reads the raw model output: temperature, top_p, top_k, seed and the
+        penalty arguments are accepted and ignored; it excludes logprobs, return_logits, prompt_logprobs, guides, logit_bias and
+        forbidden_tokens, and needs stop tokens and max_tokens > 0 (ValueError).
+        guided_regex / guided_choice / guided_json (at most one): the generated text must match the pattern, be one of the strings,
         or be compact JSON that satisfies the schema (chirrup_amd/guided.py for the subsets; GuideError, a ValueError, otherwise).  The
         request then ends "stop" exactly when its text matches; it needs stop tokens."""
         assert not (state is not None and prefill_tokens is None), "prefill_tokens cannot be None when state is not None"
@@ -272,6 +278,8 @@ class AsyncEngineCore:
         if bad:
             raise ValueError(f"logit_bias: token id {bad[0]} is outside the vocabulary (size {self.vocab_size})")
         guide = _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json)
+        if beam_width and self.max_choices is not None and beam_width > self.max_choices:
+            raise ValueError(f"beam_width {beam_width} exceeds a worker's slot count ({self.max_choices})")
         if not prefill_tokens:
             prefill_tokens = self.tokenizer.encode(prompt_str)
         task_id = task_id or str(uuid.uuid4())
@@ -288,7 +296,8 @@ class AsyncEngineCore:
                                      stop_tokens=stop_tokens, forbidden_tokens=forbidden_tokens, max_tokens=max_tokens,
                                      cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                                      return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
-                                     logit_bias=logit_bias, prompt_logprobs=prompt_logprobs, guide=guide)
+                                     logit_bias=logit_bias, prompt_logprobs=prompt_logprobs, guide=guide, beam_width=beam_width,
+                                     length_penalty=length_penalty, beam_n_best=beam_n_best)
 
     def embed(self, prompt_str: Optional[str] = None, prefill_tokens: Optional[List[int]] = None, pooling: str = "mean",
               normalize: bool = True, pad_zero: bool = True, priority: int = 0) -> "asyncio.Future":
@@ -350,6 +359,8 @@ class AsyncEngineCore:
             raise ValueError(f"n must be an integer in [1, {self.max_choices}] (a worker's slot count), got {n!r}")
         if n == 1:
             return [self.completion(prompt_str, prefill_tokens=prefill_tokens, **kw)]
+        if kw.get("beam_width"):
+            raise ValueError("n > 1 cannot be combined with beam search: beam_n_best is the number of hypotheses returned")
         if kw.get("prompt_logprobs") is not None:
             raise ValueError("n > 1 cannot be combined with prompt_logprobs")
         if kw.get("max_tokens", DEFAULT_SAMPLING_CONFIG["max_tokens"]) == 0:

@@ -32,7 +32,8 @@ from .remote_arena import WIRE_KEY, PeerArenas, RemoteStateRef, is_wire_row
 _TASK_FIELDS = ("prompt_str", "prefill_tokens", "state", "task_id", "priority", "temperature", "top_p", "top_k", "presence_penalty",
                 "frequency_penalty", "penalty_decay", "max_tokens", "stop_tokens", "forbidden_tokens", "cache_prefill",
                 "cache_prefill_padding", "return_logits", "logprobs", "top_logprobs", "seed", "logit_bias",
-                "prompt_logprobs", "choice_index", "guide", "embed", "embed_skip", "embed_normalize")
+                "prompt_logprobs", "choice_index", "guide", "embed", "embed_skip", "embed_normalize", "beam_width", "length_penalty",
+                "beam_n_best")
 _RESULT_FIELDS = ("request_status", "generated_tokens", "decoded_texts", "prefill_tokens", "error")
 
 

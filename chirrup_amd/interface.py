@@ -2,7 +2,8 @@
 
 Same surface as the reference's chirrup/interface.py:31-142: an async iterator over
 ("token", id, text[, logits[, logprobs]]) / ("cache_prefill", {"state", "prefilled_tokens"}) / ("prompt_logprobs", {"start",
-"token_ids", "logprobs", "top_logprobs"}) / ("embedding", {"embedding", "pooled_tokens", "prompt_tokens"}) events, lazily
+"token_ids", "logprobs", "top_logprobs"}) / ("embedding", {"embedding", "pooled_tokens", "prompt_tokens"}) / ("beams", {"hypotheses",
+"prompt_tokens"}) events, lazily
 submitting its Task on first iteration, with ``get_full_completion()`` and ``abort()``."""
 import asyncio
 import queue
@@ -23,7 +24,8 @@ class AsyncEngineCompletion:
                  cache_prefill_padding: int = 0, return_logits: bool = False, task_event_queue=None,
                  logprobs: bool = False, top_logprobs: int = 0, seed: Optional[int] = None,
                  logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None, guide=None,
-                 embed: Optional[str] = None, embed_skip: int = 0, embed_normalize: bool = True):
+                 embed: Optional[str] = None, embed_skip: int = 0, embed_normalize: bool = True, beam_width: int = 0,
+                 length_penalty: float = 1.0, beam_n_best: int = 1):
         self.task_id = task_id
         # the worker polls it for ("abort", None); a process-mode engine passes a channel that reaches the worker's process
         self.task_event_queue = task_event_queue if task_event_queue is not None else queue.Queue()
@@ -36,7 +38,8 @@ class AsyncEngineCompletion:
                          cache_prefill=cache_prefill, cache_prefill_padding=cache_prefill_padding,
                          return_logits=return_logits, logprobs=logprobs, top_logprobs=top_logprobs, seed=seed,
                          logit_bias=dict(logit_bias or {}), prompt_logprobs=prompt_logprobs, guide=guide,
-                         embed=embed, embed_skip=embed_skip, embed_normalize=embed_normalize)
+                         embed=embed, embed_skip=embed_skip, embed_normalize=embed_normalize, beam_width=beam_width,
+                         length_penalty=length_penalty, beam_n_best=beam_n_best)
         self._task_queue = task_queue
         # one choice of a request with parallel choices (AsyncEngineCore.completions): the callable that submits the whole group --
         # once, whichever of its choices starts first
@@ -73,6 +76,8 @@ class AsyncEngineCompletion:
                 return ("prompt_logprobs", payload)
             if kind == "embedding":
                 return ("embedding", payload)
+            if kind == "beams":
+                return ("beams", payload)
             if kind == "error":
                 self.error = payload
                 continue

@@ -69,6 +69,8 @@ SIGNATURES = {
     "rwkv7_advance_elapsed": (_i, [_i, _i, _vp, _vp, _vp]),
     "rwkv7_copy_slot_rows": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "rwkv7_fork_states": (_i, [_i, _i, _i, _i, _i] + [_vp] * 7),
+    "rwkv7_beam_select": (_i, [_i, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "rwkv7_beam_copy_states": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "rwkv7_pool_rows": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "skinny_gemm_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "skinny_gemm_splits": (_i, [_i, _i, _i, _i]),

@@ -1521,6 +1521,147 @@ def _pool_rows_host(xo, seq, t0, slot, acc_sum, acc_last, acc_count):
         count[s] += T - a
 
 
+BEAM_MAX_W = 8             # CHIRRUP_BEAM_MAX_W
+BEAM_DESC_WORDS = 44       # CHIRRUP_BEAM_DESC_WORDS: W, S, lp row [8], ids element [8], slot [8], stop id [18]
+BEAM_OUT_WORDS = 65        # CHIRRUP_BEAM_OUT_WORDS: parent [8], rank [8], copy_src [8], id [8], score bits [8], n, fin parent / id / cum bits [8]
+BEAM_OUT_COPY = 16         # first copy_src word of a group's output record
+
+
+def beam_desc(W: int, stops, lp_rows, out_rows, slots) -> list:
+    """One group's descriptor for beam_select (BEAM_DESC_WORDS int32): width, its stop ids, and per position the row of the log-prob
+    tables, the element of the sampler's ids buffer and the slot."""
+    stops = [int(t) for t in stops]
+    if not 2 <= W <= BEAM_MAX_W or not 1 <= len(stops) or W + len(stops) > TOP_LOGPROBS_MAX:
+        raise _lib.ChirrupAmdError(f"beam_desc: W {W} with {len(stops)} stop ids is outside 2 <= W <= 8, 1 <= S, W + S <= {TOP_LOGPROBS_MAX}")
+    if not len(lp_rows) == len(out_rows) == len(slots) == W:
+        raise _lib.ChirrupAmdError("beam_desc: expected W rows, W ids elements and W slots")
+    pad = [-1] * (BEAM_MAX_W - W)
+    return ([W, len(stops)] + [int(r) for r in lp_rows] + pad + [int(r) for r in out_rows] + pad + [int(r) for r in slots] + pad
+            + stops + [-1] * (BEAM_DESC_WORDS - 26 - len(stops)))
+
+
+def beam_select(lp, cand_ids, desc, scores, ids_out, out) -> None:
+    """The next beams of every beam group of a step, on the device, in ONE launch (include/chirrup_amd.h: rwkv7_beam_select, where the
+    contract is spelled out).  lp fp32 / cand_ids int32 [R, >= K]: each row's top candidates as ops.token_logprobs returns them (views
+    with a row stride are fine, e.g. lp[:, 1:]); desc int32 [G, BEAM_DESC_WORDS] (beam_desc); scores fp32 [n_slots], ids_out int32
+    [n] (the sampler's ids buffer) and out int32 [G, BEAM_OUT_WORDS] are written in place.  CPU tensors take a plain Python form of the
+    same contract (the worker's CPU tests); GPU tensors always take the kernel."""
+    G = desc.shape[0] if desc.dim() == 2 else -1
+    if desc.dtype != torch.int32 or G < 0 or desc.shape[1] != BEAM_DESC_WORDS or not desc.is_contiguous():
+        raise _lib.ChirrupAmdError("desc: expected contiguous int32 [G, BEAM_DESC_WORDS]")
+    if out.dtype != torch.int32 or tuple(out.shape) != (G, BEAM_OUT_WORDS) or not out.is_contiguous():
+        raise _lib.ChirrupAmdError("out: expected contiguous int32 [G, BEAM_OUT_WORDS]")
+    if (lp.dtype != torch.float32 or cand_ids.dtype != torch.int32 or lp.dim() != 2 or cand_ids.dim() != 2 or lp.shape != cand_ids.shape
+            or lp.stride(1) != 1 or cand_ids.stride(1) != 1 or not 3 <= lp.shape[1] <= TOP_LOGPROBS_MAX or lp.shape[0] < 1):
+        raise _lib.ChirrupAmdError(f"lp fp32 / cand_ids int32: expected [R, 3..{TOP_LOGPROBS_MAX}] of one shape with unit column stride")
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous() or scores.numel() < 1:
+        raise _lib.ChirrupAmdError("scores: expected contiguous fp32 [n_slots]")
+    if ids_out.dtype != torch.int32 or ids_out.dim() != 1 or not ids_out.is_contiguous() or ids_out.numel() < 1:
+        raise _lib.ChirrupAmdError("ids_out: expected contiguous int32 [n]")
+    if G == 0:
+        return
+    if not lp.is_cuda:
+        return _beam_select_host(lp, cand_ids, desc, scores, ids_out, out)
+    for name, t in (("lp", lp), ("cand_ids", cand_ids), ("desc", desc), ("scores", scores), ("ids_out", ids_out), ("out", out)):
+        if not t.is_cuda:
+            raise _lib.ChirrupAmdError(f"{name}: expected a GPU tensor, got {t.device}")
+    rc = _lib.load().rwkv7_beam_select(G, lp.shape[0], lp.shape[1], _ptr(lp), lp.stride(0), _ptr(cand_ids), cand_ids.stride(0), _ptr(desc),
+                                       _ptr(scores), scores.numel(), _ptr(ids_out), ids_out.numel(), _ptr(out), _stream())
+    _lib.check(rc, "rwkv7_beam_select")
+
+
+def _beam_select_host(lp, cand_ids, desc, scores, ids_out, out):
+    import numpy as np
+
+    lpn, idn, sc, io, on = lp.numpy(), cand_ids.numpy(), scores.numpy(), ids_out.numpy(), out.numpy()     # views: written in place
+    ninf = np.float32(-np.inf)
+    for g, d in enumerate(desc.tolist()):
+        W, S = d[0], d[1]
+        K = W + S
+        rows, outs, slots, stops = d[2:2 + W], d[10:10 + W], d[18:18 + W], set(d[26:26 + max(S, 0)])
+        if (not 2 <= W <= BEAM_MAX_W or not 1 <= S <= 18 or K > TOP_LOGPROBS_MAX or K > lpn.shape[1]
+                or any(not 0 <= r < lpn.shape[0] for r in rows) or any(not 0 <= r < io.shape[0] for r in outs)
+                or any(not 0 <= r < sc.shape[0] for r in slots)):
+            continue
+        cand = []
+        with np.errstate(invalid="ignore"):
+            for b in range(W):
+                for k in range(K):
+                    cum = np.float32(sc[slots[b]]) + np.float32(lpn[rows[b], k])
+                    cand.append((ninf if np.isnan(cum) else cum, b, k))
+        cand.sort(key=lambda c: (-float(c[0]), c[1], c[2]))
+        nxt, fin = [], []
+        for pos, (cum, b, k) in enumerate(cand):
+            tok = int(idn[rows[b], k])
+            if tok in stops:
+                if pos < W and np.isfinite(cum):
+                    fin.append((b, tok, cum))
+                continue
+            nxt.append((b, tok, cum))
+            if len(nxt) == W:
+                break
+        rec = np.full(BEAM_OUT_WORDS, -1, np.int32)
+        rec[32:40] = np.array([ninf] * 8, np.float32).view(np.int32)
+        rec[40] = len(fin)
+        rec[57:65] = 0
+        for j, (b, tok, cum) in enumerate(fin):
+            rec[41 + j], rec[49 + j], rec[57 + j] = b, tok, np.array([cum], np.float32).view(np.int32)[0]
+        has = [False] * W
+        place = []
+        for b, _, _ in nxt:
+            place.append(-1 if has[b] else b)
+            has[b] = True
+        taken, new_score = [False] * W, [ninf] * W
+        for r, (b, tok, cum) in enumerate(nxt):
+            q, copy = place[r], -1
+            if q < 0:
+                q = next(p for p in range(W) if not has[p] and not taken[p])
+                taken[q], copy = True, slots[b]
+            rec[q], rec[8 + q], rec[16 + q], rec[24 + q] = b, r, copy, tok
+            rec[32 + q] = np.array([cum], np.float32).view(np.int32)[0]
+            new_score[q] = cum
+            io[outs[q]] = tok
+        for p in range(W):
+            sc[slots[p]] = new_score[p]
+        on[g] = rec
+
+
+def beam_copy_states(pool, copy_src, dst) -> None:
+    """Beam search: copies the state of slot copy_src[g, p] into slot dst[g, p] for every position whose copy_src is a slot -- the
+    table is READ ON THE DEVICE (include/chirrup_amd.h: rwkv7_beam_copy_states): the select kernel of the same stream wrote it and the
+    host has not seen it.  -1, a slot outside the pool and copy_src == dst are skipped.  pool as in fork_states; copy_src int32
+    [G, 8] (a view with a row stride is fine: out[:, BEAM_OUT_COPY:BEAM_OUT_COPY + 8]), dst int32 [G, 8] contiguous.  CPU tensors take
+    torch copies."""
+    shift, wkv, elapsed = pool
+    S = elapsed.shape[0]
+    if (copy_src.dtype != torch.int32 or dst.dtype != torch.int32 or copy_src.dim() != 2 or tuple(copy_src.shape) != tuple(dst.shape)
+            or copy_src.shape[1] != BEAM_MAX_W or copy_src.stride(1) != 1 or not dst.is_contiguous()):
+        raise _lib.ChirrupAmdError("copy_src / dst: expected int32 [G, 8], copy_src with unit column stride, dst contiguous")
+    if shift.dim() != 4 or shift.shape[1] != 2 or shift.shape[2] != S or wkv.dim() < 2 or wkv.shape[1] != S or wkv.shape[0] != shift.shape[0]:
+        raise _lib.ChirrupAmdError("beam_copy_states: expected shift [L, 2, S, C], wkv [L, S, ...], elapsed [S]")
+    G = copy_src.shape[0]
+    if G == 0:
+        return
+    if not elapsed.is_cuda:
+        pairs = [(s, d) for s, d in zip(copy_src.reshape(-1).tolist(), dst.reshape(-1).tolist()) if 0 <= s < S and 0 <= d < S and s != d]
+        if pairs:
+            s = torch.tensor([p[0] for p in pairs], dtype=torch.long)
+            d = torch.tensor([p[1] for p in pairs], dtype=torch.long)
+            for t, dim in ((shift, 2), (wkv, 1), (elapsed, 0)):
+                t.index_copy_(dim, d, t.index_select(dim, s))
+        return
+    L, _, _, C = shift.shape
+    _chk(shift, "shift", torch.float16)
+    _chk(wkv, "wkv", torch.float16, (L, S, C // HEAD_SIZE, HEAD_SIZE, HEAD_SIZE))
+    _chk(elapsed, "elapsed", torch.int32, (S,))
+    _chk(dst, "dst", torch.int32)
+    if not copy_src.is_cuda:
+        raise _lib.ChirrupAmdError(f"copy_src: expected a GPU tensor, got {copy_src.device}")
+    rc = _lib.load().rwkv7_beam_copy_states(G, L, S, C, C // HEAD_SIZE, _ptr(copy_src), copy_src.stride(0), _ptr(dst), _ptr(shift),
+                                            _ptr(wkv), _ptr(elapsed), _stream())
+    _lib.check(rc, "rwkv7_beam_copy_states")
+
+
 def lora_act_(hbuf, first_plane: int) -> None:
     """hbuf [n, rows, D] fp16, planes first_plane.. of [v, w, a, g]: tanh on w, sigmoid on g."""
     _chk16("hbuf", hbuf)

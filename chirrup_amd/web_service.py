@@ -15,6 +15,7 @@ Not here: the settings CLI and the batch translate / rollout routes (out of scop
 import asyncio
 import base64
 import json
+import math
 import re
 import time
 import uuid
@@ -24,7 +25,7 @@ from fastapi import FastAPI, HTTPException
 from fastapi.responses import StreamingResponse
 from pydantic import BaseModel, Field, model_validator
 
-from .core_structure import DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, EMBED_POOLINGS, LOGIT_BIAS_MAX, RequestStatus
+from .core_structure import BEAM_K_MAX, DEFAULT_SAMPLING_CONFIG, DEFAULT_STOP_TOKENS, EMBED_POOLINGS, LOGIT_BIAS_MAX, RequestStatus
 from .guided import GuideError
 from .state_cache import SimpleStateCache
 
@@ -83,6 +84,46 @@ def guided_arguments(engine, request, thinking: bool = False) -> Dict[str, Any]:
     return kw
 
 
+BEAM_WIDTH_DEFAULT = 4
+
+
+def beam_arguments(engine, request, logprobs: bool, thinking: bool = False, n: int = 1) -> Dict[str, Any]:
+    """The engine keywords of a request's beam-search fields ({} without use_beam_search); every combination beam search excludes
+    answers 400 with the conflict named, before anything is queued."""
+    if not request.use_beam_search:
+        if request.beam_width is not None:
+            raise HTTPException(status_code=400, detail="beam_width needs use_beam_search: true")
+        return {}
+    W = request.beam_width if request.beam_width is not None else BEAM_WIDTH_DEFAULT
+    conflicts = [name for name, on in (("stream", request.stream), ("logprobs", logprobs), ("logit_bias", bool(request.logit_bias)),
+                                       ("guided_regex", request.guided_regex is not None),
+                                       ("guided_choice", request.guided_choice is not None),
+                                       ("response_format", request.response_format is not None
+                                        and request.response_format.get("type") != "text"),
+                                       ("max_tokens = 0", request.max_tokens == 0),
+                                       ("a :thinking model", thinking)) if on]
+    if conflicts:
+        raise HTTPException(status_code=400, detail=f"beam search cannot be combined with {', '.join(conflicts)}")
+    if not math.isfinite(request.length_penalty):
+        raise HTTPException(status_code=400, detail="length_penalty must be a finite number")
+    slots = getattr(engine, "max_choices", None)
+    if slots is not None and W > slots:
+        raise HTTPException(status_code=400, detail=f"beam_width = {W} exceeds the {slots} slots a worker holds")
+    if not 1 <= n <= W:
+        raise HTTPException(status_code=400, detail=f"n = {n} with beam search must be in 1..beam_width ({W}): it is the number of hypotheses returned")
+    return {"beam_width": W, "length_penalty": float(request.length_penalty), "beam_n_best": n}
+
+
+def check_beam_stops(beam: Dict[str, Any], stop_tokens) -> None:
+    """400 when a beam request's distinct stop tokens do not fit beside its beams in the BEAM_K_MAX candidates of a row (both routes)."""
+    if not beam:
+        return
+    room, have = BEAM_K_MAX - beam["beam_width"], len(set(stop_tokens))
+    if have > room:
+        raise HTTPException(status_code=400, detail=f"beam search: beam_width {beam['beam_width']} leaves room for {room} stop tokens, "
+                            f"the request has {have}")
+
+
 class ChatCompletionRequest(BaseModel):                      # api_model.py:14-62: same fields, defaults and ranges
     model: str = "rwkv-latest"
     messages: List[ChatMessage]
@@ -113,6 +154,12 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
     response_format: Optional[Dict[str, Any]] = None
+    # beam search (extension fields, as in other open servers): use_beam_search turns it on with beam_width beams (2..8, default 4)
+    # and length_penalty; the request is not sampled -- temperature, top_p, seed and the penalties are accepted and ignored -- and
+    # cannot stream or carry logprobs, logit_bias or a guide (400)
+    use_beam_search: bool = False
+    beam_width: Optional[int] = Field(None, ge=2, le=8)
+    length_penalty: float = 1.0
 
     @model_validator(mode="after")
     def _top_logprobs_needs_logprobs(self):
@@ -156,6 +203,12 @@ class CompletionRequest(BaseModel):
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
     response_format: Optional[Dict[str, Any]] = None
+    # beam search (extension fields, as in other open servers): use_beam_search turns it on with beam_width beams (2..8, default 4)
+    # and length_penalty; the request is not sampled -- temperature, top_p, seed and the penalties are accepted and ignored -- and
+    # cannot stream or carry logprobs, logit_bias or a guide (400)
+    use_beam_search: bool = False
+    beam_width: Optional[int] = Field(None, ge=2, le=8)
+    length_penalty: float = 1.0
 
     @model_validator(mode="after")
     def _fields(self):
@@ -307,6 +360,22 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                 if node is not None:
                     await state_cache.awake_hang_up_prefills(key)
 
+    async def beam_payload(completion, head):
+        """The ("beams", ...) payload of a beam-search completion; the prefix-cache hand-over as in events_of."""
+        payload = None
+        async for ev in completion:
+            if ev[0] == "beams":
+                payload = ev[1]
+            elif ev[0] == "cache_prefill" and state_cache is not None:
+                key = tuple(head) + tuple(ev[1]["prefilled_tokens"])
+                if state_cache.cache(key, ev[1]["state"], return_trie_node=True) is not None:
+                    await state_cache.awake_hang_up_prefills(key)
+        if completion.error:
+            raise HTTPException(status_code=500, detail=f"generation failed: {completion.error}")
+        if payload is None:
+            raise HTTPException(status_code=500, detail=f"beam search ended without hypotheses ({completion.task.request_status})")
+        return payload
+
     @app.post("/v1/chat/completions")
     async def chat(request: ChatCompletionRequest):
         if not engine.is_initialized or engine.is_shutdown:
@@ -315,8 +384,9 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         vocab = getattr(engine, "vocab_size", None)
         if vocab is not None and bias and max(bias) >= vocab:
             raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        beam = beam_arguments(engine, request, request.logprobs, thinking="thinking" in request.model.split(":"), n=request.n)
         guided = guided_arguments(engine, request, thinking="thinking" in request.model.split(":"))
-        n = request.n
+        n = 1 if beam else request.n                            # (with beam search n counts hypotheses of ONE request)
         if n > 1 and n > (getattr(engine, "max_choices", None) or 1):
             raise HTTPException(status_code=400, detail=f"n = {n} exceeds the {getattr(engine, 'max_choices', None) or 1} choices a worker holds")
         try:
@@ -325,6 +395,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
             stops: List[int] = []
             for word in ([request.stop] if isinstance(request.stop, str) else (request.stop or [])):
                 stops.extend(engine.tokenizer.encode(word))
+            check_beam_stops(beam, DEFAULT_STOP_TOKENS + stops)
             rest, state, n_cached = tokens, None, 0
             if request.use_state_cache and state_cache is not None:
                 rest, state, n_cached = await state_cache.check_and_wait_prefill(tokens, pad)
@@ -335,12 +406,30 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                       cache_prefill=state_cache is not None and request.cache_prefill, cache_prefill_padding=pad,
                       **({"logprobs": True, "top_logprobs": request.top_logprobs or 0} if request.logprobs else {}),
                       **({"seed": request.seed} if request.seed is not None else {}),
-                      **({"logit_bias": bias} if bias else {}), **guided)
+                      **({"logit_bias": bias} if bias else {}), **guided, **beam)
             choices = engine.completions(n=n, **kw) if n > 1 else [engine.completion(**kw)]      # one prefill for the n choices
         except HTTPException:
             raise
         except Exception as e:                                  # noqa: BLE001 -- app.py:231
             raise HTTPException(status_code=500, detail=f"generation failed: {e}")
+        if beam:
+            try:
+                payload = await beam_payload(choices[0], tokens[:n_cached])
+            finally:
+                choices[0].abort()
+                if state_cache is not None and request.use_state_cache and n_cached + pad != len(tokens):
+                    await state_cache.awake_hang_up_prefills(tuple(tokens[:-pad]) if pad else tuple(tokens))
+            out = []
+            for j, h in enumerate(payload["hypotheses"]):       # rank order; the splitter applies the route's content rules
+                sp = ThinkSplitter()
+                sp.feed(prompt.split("\n\n")[-1])
+                parts = sp.feed(h["text"])
+                out.append({"index": j, "finish_reason": h["finish_reason"],
+                            "message": {"role": "assistant", "content": "".join(p for p, st in parts if st == "content"),
+                                        "reasoning_content": "".join(p for p, st in parts if st == "reasoning_content")}})
+            n_out = sum(len(h["token_ids"]) for h in payload["hypotheses"])
+            return {"id": f"chatcmpl-{uuid.uuid4().hex}", "object": "chat.completion", "created": int(time.time()), "model": request.model,
+                    "choices": out, "usage": {"prompt_tokens": len(tokens), "completion_tokens": n_out, "total_tokens": len(tokens) + n_out}}
         splitters = [ThinkSplitter() for _ in choices]
         for splitter in splitters:
             splitter.feed(prompt.split("\n\n")[-1])             # the assistant cue sets the splitter's starting part (app.py:243)
@@ -446,6 +535,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
         vocab = getattr(engine, "vocab_size", None)
         if vocab is not None and bias and max(bias) >= vocab:
             raise HTTPException(status_code=400, detail=f"logit_bias: token id {max(bias)} is outside the vocabulary (size {vocab})")
+        beam = beam_arguments(engine, request, request.logprobs is not None)
         guided = guided_arguments(engine, request)
         k, skip = request.logprobs, (1 if request.pad_zero else 0)      # skip: the token 0 in front is fed, not echoed
         score_prompt = request.echo and k is not None
@@ -468,6 +558,7 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
             raise
         except Exception as e:                                  # noqa: BLE001
             raise HTTPException(status_code=500, detail=f"generation failed: {e}")
+        check_beam_stops(beam, DEFAULT_STOP_TOKENS + stops)
         cid, created_at = f"cmpl-{uuid.uuid4().hex}", int(time.time())
         # every prompt position must be fed to be scored: no prefix-state cache lookup then (the state may still be exported)
         use_cache = state_cache is not None and request.use_state_cache and not score_prompt
@@ -497,8 +588,13 @@ def create_app(engine, state_cache: Optional[SimpleStateCache] = None, state_cac
                                      **({"logprobs": True, "top_logprobs": k} if k is not None and request.max_tokens > 0 else {}),
                                      **({"prompt_logprobs": k} if score_prompt else {}),
                                      **({"seed": request.seed} if request.seed is not None else {}),
-                                     **({"logit_bias": bias} if bias else {}), **guided)
+                                     **({"logit_bias": bias} if bias else {}), **guided, **beam)
             completions_.append(comp)
+            if beam:                                            # choices[index] is the best hypothesis, behind the prompt with echo
+                payload = await beam_payload(comp, toks[:n_cached])
+                best = payload["hypotheses"][0] if payload["hypotheses"] else {"text": "", "finish_reason": "length", "token_ids": []}
+                return {"text": echo_text + best["text"], "index": index, "logprobs": None, "finish_reason": best["finish_reason"],
+                        "n_out": len(best["token_ids"])}
             plp: List[Any] = [None] * len(toks)
             n_plp, gen, gen_text = 0, [], []
             sent_head = False

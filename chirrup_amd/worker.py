@@ -9,6 +9,7 @@ Keeps the reference worker's protocol and scheduling semantics (chirrup/worker.p
     most ``max(batch_size/8, 1)`` sequences (:143, :744-776, :854-856);
   * messages: ("token_generated", (id, text[, logits])) -- (id, text, logits or None, logprobs) for a request with
     ``logprobs`` --, ("task_completed", task),
+    ("beams", {"hypotheses", "prompt_tokens"}) instead of token messages for a beam-search request (DESIGN.md "Beam search"),
     ("cache_prefill", {"state", "prefilled_tokens"}) on the task's output queue (:422-434, :498-501,
     :556-558), (worker_id, "worker_loaded" | "worker_performance", {...}) on the worker event queue.
 
@@ -31,7 +32,9 @@ What is different is the DEVICE DISPATCH, redesigned for a 288 GB MI355X:
     dropped (the slot is recycled afterwards, in stream order).  ``run_ahead=False`` handles each forward's ids in
     the same ``step()`` call, like the reference's loop; both modes produce the same token streams.
 """
+import math
 import queue
+import struct
 import time
 import types
 from collections import deque
@@ -81,9 +84,17 @@ def _empty_slot() -> dict:
     # plp_prompt = the tokens as admitted, plp_next = index of the next one to feed, plp_sent = positions already sent.
     # Parallel choices: siblings = [(slot, task)] of the choices waiting suspended for this slot's prefill (until the fork); orphan:
     # choice 0 has aborted and the slot prefills on for its live siblings only.  emb_fed: prompt positions an embedding request has fed
-    return {"emb_fed": 0, "task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
+    # beam: (group, position) of a slot that holds one beam of a beam-search request, from the fork to the request's end
+    return {"beam": None, "emb_fed": 0, "task": None, "is_prefilling": None, "new_token": None, "next_input_token": None,
             "state_category": StateCategory.EMPTY, "prefilled_tokens": [], "prefill_cached": False,
             "feedback": False, "plp_prompt": None, "plp_next": 0, "plp_sent": 0, "siblings": None, "orphan": False}
+
+
+class _NullSink:
+    """The output queue of the internal tasks that hold the further slots of a beam-search request: nobody reads their messages."""
+
+    def put_nowait(self, msg):
+        pass
 
 
 class GuidePool:
@@ -216,6 +227,13 @@ class Worker:
         self._emb = None
         self._emb_host = None
         self._emb_downloads = 0
+        # beam search (DESIGN.md "Beam search"): beam_scores fp32 [slots] is the device's score table; _beam_host: two pinned sets of
+        # the per-step outputs (the loop runs one forward ahead of the host); beam_trace: every record also carries the step's
+        # downloaded candidate tables (tests replay the contract from them)
+        self.beam_trace = False
+        self._beam_host = None
+        self._beam_tables: Dict[tuple, tuple] = {}
+        self._beam_live = 0                           # forked beam groups that have not ended: 0 keeps every step off the beam path
 
     # ------------------------------------------------------------------ set-up
     def _load_model(self):
@@ -270,6 +288,7 @@ class Worker:
         self._bias_n = [0] * n
         # device-side feedback of the sampled ids (run-ahead): next decode inputs and the penalty bookkeeping
         self.last_ids = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.beam_scores = torch.zeros((n,), **f32)
         self.penalty_weight = torch.ones((V,), **f32)           # occurrence increment per token id (worker.py:531)
         self.penalty_weight[[t for t in self.no_penalty_token_ids if t < V]] = 0.0
         self._ids_host = ([torch.zeros((n + 1,), dtype=torch.int32).pin_memory() for _ in range(2)]     # (+ 1: the launch-status word)
@@ -448,6 +467,8 @@ class Worker:
             td = self.state_slot[slot]
             if td["task"] is not task or RequestStatus.is_finished(task.request_status):
                 continue
+            if td["beam"] is not None:                      # a beam row: its group is handled below, as a whole
+                continue
             entry = None
             if lp is not None and j in lp_pos:
                 v, i, k = lp_val[lp_pos[j]], lp_ids[lp_pos[j]], task.top_logprobs
@@ -455,6 +476,10 @@ class Worker:
             self._handle_forward_one_decode_phase(td, int(host_ids[j]), rec["raw"].get(j), entry)
             if RequestStatus.is_finished(task.request_status):
                 done.append(slot)
+        beam = rec.get("beam")
+        if beam is not None:
+            for group, row in zip(beam["groups"], beam["out"].tolist()):
+                self._handle_beam_step(group, row, done)
         self._process_accomplished_tasks(done)
 
     def _handle_prompt_logprobs(self, plp):
@@ -623,11 +648,26 @@ class Worker:
                 task: Task = self.task_queue.get_nowait()
             except queue.Empty:
                 return None
+            if task.beam_width and not task.siblings:
+                self._make_beam_members(task)
             if 1 + len(task.siblings) <= self.max_batch_size:
                 return task
             for t in [task] + task.siblings:
                 t.request_status = RequestStatus.FINISHED_ABORTED
                 t.output_queue.put_nowait(("task_completed", t))
+
+    def _make_beam_members(self, task: Task) -> None:
+        """A beam-search request of width W rides the parallel-choices path: W - 1 internal tasks (no client: _NullSink) are its
+        siblings until it ends, so admission, the single prefill, the prefix cache and the fork are those of n = W choices."""
+        task.beam_prompt_tokens = len(task.prefill_tokens)   # the tokens fed: behind a prefix-cache hit, the uncached remainder
+        members = []
+        for j in range(1, task.beam_width):
+            t = Task(output_queue=_NullSink(), task_event_queue=queue.Queue(), prompt_str="", prefill_tokens=list(task.prefill_tokens),
+                     state=None, task_id=f"{task.task_id}:beam{j}", temperature=0.0, presence_penalty=0.0, frequency_penalty=0.0,
+                     penalty_decay=1.0, max_tokens=task.max_tokens, stop_tokens=list(task.stop_tokens), choice_index=j)
+            t.beam_leader = task
+            members.append(t)
+        task.siblings = members
 
     def _admit_group(self, task: Task, slot: int) -> bool:
         """Parallel choices: choice 0 into `slot` (every slot before it is taken), choices 1..n-1 into the next free slots, suspended
@@ -702,6 +742,143 @@ class Worker:
                                           next_input_token=td["next_input_token"], prefilled_tokens=list(td["prefilled_tokens"]))
             if td["orphan"]:
                 self.state_slot[p] = _empty_slot()
+            elif td["task"].beam_width:
+                self._start_beam(p, td, live)
+
+    # ------------------------------------------------------------------ beam search
+    @staticmethod
+    def _is_beam_task(task: Task) -> bool:
+        return task.beam_width > 0 or getattr(task, "beam_leader", None) is not None
+
+    def _start_beam(self, p: int, td, live) -> None:
+        """The group has forked: position 0 is the leader's slot, positions 1.. the members' slots (ascending).  Position 0 starts
+        at score +0, the others at -inf (stream-ordered fills), so the first step chooses among position 0's candidates only."""
+        task: Task = td["task"]
+        slots, tasks = [p] + [s for s, _ in live], [task] + [t for _, t in live]
+        assert len(slots) == task.beam_width
+        group = {"task": task, "slots": slots, "tasks": tasks, "W": task.beam_width, "stops": sorted(set(task.stop_tokens)),
+                 "parents": [], "ids": [], "hyps": [], "done": False}
+        group["K"] = group["W"] + len(group["stops"])
+        for pos, s in enumerate(slots):
+            self.state_slot[s]["beam"] = (group, pos)
+            self.beam_scores[s] = 0.0 if pos == 0 else float("-inf")
+        self._beam_live += 1
+
+    def _abort_beam_members(self, td) -> None:
+        """The leader of a beam-search request has aborted, before or after the fork: its members end with it (their slots follow
+        the leader's in the slot loop of step(), which releases them)."""
+        members = [t for _, t in td["siblings"] or ()]
+        if td["beam"] is not None:
+            td["beam"][0]["done"] = True
+            members = td["beam"][0]["tasks"][1:]
+            self._beam_live -= 1
+        for t in members:
+            t.request_status = RequestStatus.FINISHED_ABORTED
+        td["task"].siblings = []
+
+    def _beam_step_tables(self, groups, decode_slots):
+        """(desc [G, BEAM_DESC_WORDS], the groups' decode rows [R], dst slots [G, 8]) on the device and (first row, W, K) per group, for
+        the beam groups of a step; uploaded once per batch composition (pinned, non-blocking) and cached like _slot_tensor."""
+        where = {s: j for j, s in enumerate(decode_slots)}
+        desc, rows, dst, spans = [], [], [], []
+        for g in groups:
+            W, out_rows = g["W"], [where[s] for s in g["slots"]]
+            desc.append(ops.beam_desc(W, g["stops"], list(range(len(rows), len(rows) + W)), out_rows, g["slots"]))
+            spans.append((len(rows), W, g["K"]))
+            rows.extend(out_rows)
+            dst.append(list(g["slots"]) + [-1] * (ops.BEAM_MAX_W - W))
+        key = tuple(v for d in desc for v in d)
+        hit = self._beam_tables.get(key)
+        if hit is None:
+            if len(self._beam_tables) >= 16:
+                self._beam_tables.pop(next(iter(self._beam_tables)))
+            d, r, t = self._upload_int32([v for x in desc for v in x], rows, [v for x in dst for v in x])
+            hit = self._beam_tables[key] = (d.view(len(groups), ops.BEAM_DESC_WORDS), r, t.view(len(groups), ops.BEAM_MAX_W))
+        return hit + (spans,)
+
+    def _download_beam(self, groups, spans, bout, bv, bi):
+        """The beam part of a record: the step's output records (and, with beam_trace, its candidate tables) copied into pinned host
+        memory behind the record's event; two sets used in turn, like the ids."""
+        part = {"groups": groups, "spans": spans, "out": bout, "lp": None, "ids": None}
+        trace = self.beam_trace
+        if self.device.type != "cuda":
+            if trace:
+                part["lp"], part["ids"] = bv[:, 1:].clone(), bi.clone()
+            return part
+        if self._beam_host is None:
+            n, k = self.real_state_size, ops.TOP_LOGPROBS_MAX
+            self._beam_host = [(torch.empty((n * ops.BEAM_OUT_WORDS,), dtype=torch.int32).pin_memory(),
+                                torch.empty((n * (k + 1),), dtype=torch.float32).pin_memory(),
+                                torch.empty((n * k,), dtype=torch.int32).pin_memory()) for _ in range(2)]
+        ho, hv, hi = self._beam_host[self._launches & 1]
+        part["out"] = ho[:bout.numel()].view(bout.shape).copy_(bout, non_blocking=True)
+        if trace:
+            part["lp"] = hv[:bv.numel()].view(bv.shape).copy_(bv, non_blocking=True)[:, 1:]
+            part["ids"] = hi[:bi.numel()].view(bi.shape).copy_(bi, non_blocking=True)
+        return part
+
+    def _beam_path(self, group, t: int, p: int) -> List[int]:
+        """The tokens of the beam in position p after step t (t = 0: none), by backtracking the trellis."""
+        toks = []
+        for i in range(t - 1, -1, -1):
+            toks.append(group["ids"][i][p])
+            p = group["parents"][i][p]
+        return toks[::-1]
+
+    def _handle_beam_step(self, group, row: List[int], done: List[int]) -> None:
+        """Host half of one beam step, one forward behind like every row: extends the trellis, collects the hypotheses the step
+        finished, and ends the request after the first step with at least W finished hypotheses or after step max_tokens (every
+        live beam with a finite score then ends "length")."""
+        task: Task = group["task"]
+        if group["done"] or RequestStatus.is_finished(task.request_status):
+            return
+        def f32(bits: int) -> float:              # the binary32 value a record carries as an int32 word
+            return struct.unpack("<f", struct.pack("<i", bits))[0]
+
+        W = group["W"]
+        group["parents"].append(row[0:W])
+        group["ids"].append(row[24:24 + W])
+        t = len(group["ids"])
+        for j in range(row[40]):
+            group["hyps"].append({"tokens": self._beam_path(group, t - 1, row[41 + j]), "cum": f32(row[57 + j]), "reason": "stop",
+                                  "step": t, "order": j})
+        if t >= task.max_tokens:
+            for p in range(W):
+                score = f32(row[32 + p])
+                if row[p] >= 0 and math.isfinite(score):
+                    group["hyps"].append({"tokens": self._beam_path(group, t, p), "cum": score, "reason": "length", "step": t,
+                                          "order": W + row[8 + p]})
+        elif len(group["hyps"]) < W:
+            return
+        self._finish_beam(group, done)
+
+    def _finish_beam(self, group, done: List[int]) -> None:
+        """Ranks the hypotheses (cum / max(T, 1) ** length_penalty in binary64; ties: finished earlier, then lower rank), sends the
+        one ("beams", ...) message and releases the W slots."""
+        task: Task = group["task"]
+        lam = task.length_penalty
+        for h in group["hyps"]:
+            h["score"] = h["cum"] / (float(max(len(h["tokens"]), 1)) ** lam)
+        ranked = sorted(group["hyps"], key=lambda h: (-h["score"], h["step"], h["order"]))[:task.beam_n_best]
+        out = []
+        for h in ranked:
+            try:
+                text = self.tokenizer.decode(h["tokens"], utf8_errors="ignore")
+            except KeyError:             # an id the vocabulary file does not define (the model's vocab is padded)
+                text = ""
+            out.append({"token_ids": list(h["tokens"]), "text": text, "cumulative_logprob": h["cum"], "score": h["score"],
+                        "finish_reason": h["reason"]})
+        if out:
+            task.generated_tokens, task.decoded_texts = list(out[0]["token_ids"]), [out[0]["text"]]
+        stopped = bool(out) and out[0]["finish_reason"] == "stop"
+        task.request_status = RequestStatus.FINISHED_STOPPED if stopped else RequestStatus.FINISHED_LENGTH_CAPPED
+        task.output_queue.put_nowait(("beams", {"hypotheses": out, "prompt_tokens": getattr(task, "beam_prompt_tokens", 0)}))
+        group["done"] = True
+        self._beam_live -= 1
+        for t in group["tasks"][1:]:
+            t.request_status = task.request_status
+        task.siblings = []
+        done.extend(group["slots"])
 
     def _install(self, task: Task, slot: int):
         s0, s1, s2 = self.batch_state
@@ -782,15 +959,16 @@ class Worker:
         self.alpha_presence_vector[slot].zero_()
         if getattr(self, "_pen_lists", None) is not None:
             self._pen_lists.reset(slot)
+        beam = self._is_beam_task(task)          # the search reads the raw output: zero penalties, no draw, no seed
         self.temperature_tensor[slot, 0] = task.temperature if task.temperature > 0 else 1.0
         self.top_p_tensor[slot, 0] = task.top_p
         self.top_k_tensor[slot, 0] = task.top_k
-        self.frequency_penalty_tensor[slot, 0] = task.frequency_penalty
-        self.penalty_decay_tensor[slot, 0] = task.penalty_decay
-        self.presence_penalty_tensor[slot, 0] = task.presence_penalty
-        self._greedy[slot] = is_greedy_row(task.temperature, task.top_p, task.top_k)
+        self.frequency_penalty_tensor[slot, 0] = 0.0 if beam else task.frequency_penalty
+        self.penalty_decay_tensor[slot, 0] = 1.0 if beam else task.penalty_decay
+        self.presence_penalty_tensor[slot, 0] = 0.0 if beam else task.presence_penalty
+        self._greedy[slot] = beam or is_greedy_row(task.temperature, task.top_p, task.top_k)
         # stream-ordered writes: a run-ahead row of the slot's previous request still in flight reads (and advances) the old values
-        seeded = task.seed is not None
+        seeded = task.seed is not None and not beam
         if seeded or self._seeded[slot]:
             self.seeds[slot] = ops.seed_int64(task.seed) if seeded else 0
             self.seeded[slot] = 1 + task.choice_index if seeded else 0     # Philox stream of the choice
@@ -861,6 +1039,11 @@ class Worker:
         if lp_rows:
             lp_idx = self._slot_tensor(lp_rows)
             lp_k = max(self.state_slot[decode_slots[j]]["task"].top_logprobs for j in lp_rows)
+        # beam groups of the step (all W slots of a forked group decode together until it ends): their tables, before the forward
+        b_groups = ([td["beam"][0] for td in (self.state_slot[s] for s in decode_slots) if td["beam"] is not None and td["beam"][1] == 0]
+                    if self._beam_live else [])
+        if b_groups:
+            b_desc, b_rows, b_dst, b_spans = self._beam_step_tables(b_groups, decode_slots)
         tokens = []
         for j, s in enumerate(slots):
             td = self.state_slot[s]
@@ -880,6 +1063,9 @@ class Worker:
             # before the next forward can overwrite a graph's static output buffer
             pv, pi = ops.token_logprobs(out, p_k, targets=p_targets_dev, rows=p_rows_dev)
             plp = self._download_plp(p_entries, pv, pi)
+        if b_groups:
+            # the K = W + S most likely ids of each beam row and their log-probabilities, of the raw output: before any edit below
+            bv, bi = ops.token_logprobs(out, max(g["K"] for g in b_groups), rows=b_rows)
         if nd == 0:
             if plp is None:
                 return None
@@ -929,7 +1115,15 @@ class Worker:
                     drawn[k] = sample_inverse_cdf(logits[lrows[k]], self.temperature_tensor[srows[k]], self.top_p_tensor[srows[k]],
                                                   self.top_k_tensor[srows[k]], u[k])
                 ids[lrows] = drawn.to(torch.int32)
+        if b_groups:
+            # the next beams, on the device: their ids replace the beam rows' arg-max ids before the commit feeds them back, and
+            # the states the selection moves are copied behind the commit and before the next forward -- no host round trip
+            # (filled with -1: a group the kernel refuses writes nothing, and its record then reads as no beams and no hypotheses)
+            bout = torch.full((len(b_groups), ops.BEAM_OUT_WORDS), -1, dtype=torch.int32, device=self.device)
+            ops.beam_select(bv[:, 1:], bi, b_desc, self.beam_scores, ids, bout)
         self._commit_sampled(ids, didx, status_out)
+        if b_groups:
+            ops.beam_copy_states(self.batch_state, bout[:, ops.BEAM_OUT_COPY:ops.BEAM_OUT_COPY + ops.BEAM_MAX_W], b_dst)
         if g_rows:                                         # the sampled ids move the guided slots' states, on the device
             ops.guide_advance(g_idx, didx, ids, self._guides.tok_off, self._guides.tok_bytes, self._guides.next, self._guides.state)
         lp = None
@@ -952,11 +1146,17 @@ class Worker:
                 n_lp = len(lp_rows)
                 lp[1] = hv[:lp_val.numel()].view(n_lp, lp_k + 1).copy_(lp_val, non_blocking=True)
                 lp[2] = hi[:lp_ids.numel()].view(n_lp, lp_k).copy_(lp_ids, non_blocking=True)
+            if b_groups:
+                beam = self._download_beam(b_groups, b_spans, bout, bv, bi)
             event = torch.cuda.Event()
             event.record()
             ids = host
+        elif b_groups:
+            beam = self._download_beam(b_groups, b_spans, bout, bv, bi)
         rec = {"rows": [(s, self.state_slot[s]["task"]) for s in decode_slots], "ids": ids, "event": event, "raw": raw,
                "status": status_out is not None and self._ids_host is not None}
+        if b_groups:
+            rec["beam"] = beam
         if lp is not None:
             rec["lp"] = lp
         if plp is not None:
@@ -1082,9 +1282,11 @@ class Worker:
             assert cat != StateCategory.FINISHED
             if cat == StateCategory.EMPTY:
                 continue
-            if self._is_task_aborted(td) and not (td["siblings"] and self._orphan_on_abort(td)):
+            if self._is_task_aborted(td) and not (td["siblings"] and not td["task"].beam_width and self._orphan_on_abort(td)):
                 td["task"].request_status = RequestStatus.FINISHED_ABORTED
                 td["state_category"] = StateCategory.FINISHED
+                if td["task"].beam_width:
+                    self._abort_beam_members(td)
             elif cat == StateCategory.FORWARD_SEQ:
                 self._handle_forward_seq(td, slot)
             elif cat == StateCategory.FORWARD_ONE_PREFILL:

@@ -565,6 +565,49 @@ int rwkv7_guide_advance(int n_rows, int n_ids, int V, int P, const int32_t *rows
                         int32_t *guide_state, void *stream);
 
 /*
+ * Beam search (DESIGN.md "Beam search").  A beam group of width W (2..CHIRRUP_BEAM_MAX_W) with S stop ids (S >= 1, W + S <= 20) holds
+ * W slots of the worker's state tables, one per position.  Every step, rwkv7_token_logprobs gives each position's K = W + S most likely
+ * ids; rwkv7_beam_select picks the next beams of every group of the step on the device and rwkv7_beam_copy_states moves the states
+ * the selection asks for -- the host learns both one step late.
+ *
+ * rwkv7_beam_select: one launch, one wave per group g < n_groups.  desc int32 [n_groups][CHIRRUP_BEAM_DESC_WORDS] describes a group:
+ *   desc[0] = W, desc[1] = S, desc[2 + p] = the row of position p in lp / cand_ids, desc[10 + p] = its element of ids_out (its row of
+ *   the sampler's ids buffer), desc[18 + p] = its slot, desc[26 + j] = stop id j.
+ * lp binary32 and cand_ids int32 hold k_cols >= K columns per row (row strides lp_stride / ids_stride in elements, n_lp_rows rows):
+ * entry k of a row is the k-th candidate (logit descending, then id ascending) and its log-probability.  scores binary32 [n_slots].
+ *   Candidate (b, k): cum = scores[slot b] + lp[row b][k], one binary32 addition; a NaN cum becomes -inf.
+ *   Order: cum descending, then b ascending, then k ascending -- computed by counting, per candidate, the candidates that beat it:
+ *   independent of lane scheduling, no floating-point atomics.
+ *   Walk in that order with pos = candidates seen so far: a candidate whose id is a stop id is recorded as finished (parent b, id,
+ *   cum) iff pos < W and cum is finite, and never becomes a beam; any other candidate is the next beam of rank 0, 1, ...; the walk
+ *   ends with W next beams.
+ *   Placement in rank order: the first chosen child of parent b stays in position b; every further child takes the lowest position
+ *   whose old beam has no chosen child and gets copy_src = the slot of b.  No copy destination is a copy source.
+ * Outputs: ids_out[desc[10 + p]] = the id of position p (n_ids elements); scores[slot p] = its cum; and out int32
+ * [n_groups][CHIRRUP_BEAM_OUT_WORDS]: out[0 + p] = parent (old position), out[8 + p] = rank, out[16 + p] = copy_src (a slot, or -1),
+ * out[24 + p] = id, out[32 + p] = the bits of its score, out[40] = finished records n, out[41 + j] / out[49 + j] / out[57 + j] = parent,
+ * id and cum bits of record j < n.  Unused entries (p >= W, j >= n) are -1 (-inf bits for scores, 0 for cum).
+ * A group whose descriptor is out of range (W, S, K > k_cols, a row, element or slot outside its table) writes nothing; elements of
+ * groups that are not listed are untouched.  The slots of one launch must be distinct.  n_groups == 0 launches nothing.
+ * CHIRRUP_E_SHAPE: n_groups < 0 or > 65535, k_cols outside 3..20, a stride below k_cols, a non-positive table size.
+ *
+ * rwkv7_beam_copy_states: grid (pieces of a layer, L, n_groups * CHIRRUP_BEAM_MAX_W) like rwkv7_fork_states.  Position z = g * 8 + p reads
+ * s = copy_src[g * group_stride + p] (e.g. out + 16 of rwkv7_beam_select with group_stride CHIRRUP_BEAM_OUT_WORDS) and d = dst[z] FROM
+ * DEVICE MEMORY; when both are in [0, S) and differ, slot s of shift binary16 [L][2][S][C], wkv binary16 [L][S][H][64][64] and elapsed
+ * int32 [S] is copied to slot d, bit for bit (16 B per lane, integer vectors: NaN payloads and -0 survive); otherwise the workgroup
+ * returns at once.  Destinations must be distinct and no position's source (the placement rule guarantees it).  C == H * 64; shift
+ * and wkv 16-byte aligned; n_groups <= 8191; group_stride >= 8.  n_groups == 0 launches nothing.
+ */
+#define CHIRRUP_BEAM_MAX_W 8
+#define CHIRRUP_BEAM_DESC_WORDS 44
+#define CHIRRUP_BEAM_OUT_WORDS 65
+int rwkv7_beam_select(int n_groups, int n_lp_rows, int k_cols, const float *lp, int64_t lp_stride, const int32_t *cand_ids,
+                      int64_t ids_stride, const int32_t *desc, float *scores, int n_slots, int32_t *ids_out, int n_ids, int32_t *out,
+                      void *stream);
+int rwkv7_beam_copy_states(int n_groups, int L, int S, int C, int H, const int32_t *copy_src, int64_t group_stride, const int32_t *dst,
+                           void *shift, void *wkv, int32_t *elapsed, void *stream);
+
+/*
  * The pieces of mm8t_seq for a decode step that folds the mm8 prologue / reduce launches into the neighbouring kernels
  * (chirrup_amd/rwkv7.py, ffn_dtype = int8): LN kernel (prologue of ffn.key, rwkv7_add_ln_mix_mm8) -> mm8t_gemm_partial ->
  * mm8_reduce_rows (corrections + relu^2 of ffn.key AND the prologue of ffn.value) -> mm8t_gemm_partial -> next LN kernel
