@@ -31,6 +31,8 @@ LOGIT_BIAS_MAX = 1024          # entries of one request's logit_bias (the worker
 EMBED_POOLINGS = ("mean", "last")   # Task.embed
 BEAM_WIDTH_MAX = 8             # Task.beam_width
 BEAM_K_MAX = 20                # candidates per beam and step, beam_width + len(stop_tokens): the top-K of the log-prob kernel (ops.TOP_LOGPROBS_MAX)
+GUIDE_STACK_DEPTH_MAX = 32     # pushes a grammar guide's per-slot stack holds (guided.compile_grammar: max_depth)
+GUIDE_CALL_SITES_MAX = 255     # call sites of one grammar guide: a stack level is one byte, 0 the bottom marker
 GUIDE_MAX_STATES = 4096        # states of one guide's byte DFA (chirrup_amd/guided.py); a state is one row of the worker's guide pool
 
 

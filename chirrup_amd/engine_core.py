@@ -27,14 +27,17 @@ from .interface import AsyncEngineCompletion
 GUIDE_CACHE_SIZE = 64          # compiled guides kept by the engine, least recently used first out
 
 
-def _compiled_guide(cache: Dict[Any, Any], guided_regex, guided_choice, guided_json):
-    """The ByteDFA of the one guided_* argument given (None when none is): compiled here, on the caller's side, so that a bad
+def _compiled_guide(cache: Dict[Any, Any], guided_regex, guided_choice, guided_json, guided_grammar=None):
+    """The ByteDFA (for guided_grammar: the StackDFA) of the one guided_* argument given (None when none is): compiled here, on the caller's side, so that a bad
     pattern raises GuideError before anything is queued; a small LRU keyed by the source spares the recompilation."""
-    from .guided import GuideError, compile_choice, compile_regex, schema_to_regex
+    from .guided import GuideError, compile_choice, compile_grammar, compile_regex, schema_to_regex
 
-    given = [k for k, v in (("guided_regex", guided_regex), ("guided_choice", guided_choice), ("guided_json", guided_json)) if v is not None]
+    given = [k for k, v in (("guided_regex", guided_regex), ("guided_choice", guided_choice), ("guided_json", guided_json),
+                              ("guided_grammar", guided_grammar)) if v is not None]
     if not given:
         return None
+    if len(given) > 1 and guided_grammar is not None:
+        raise GuideError(f"at most one of guided_regex, guided_choice, guided_json and guided_grammar may be given, got {' and '.join(given)}")
     if len(given) > 1:
         raise GuideError(f"at most one of guided_regex, guided_choice and guided_json may be given, got {' and '.join(given)}")
     try:
@@ -42,6 +45,10 @@ def _compiled_guide(cache: Dict[Any, Any], guided_regex, guided_choice, guided_j
             src = ("regex", guided_regex)
         elif guided_choice is not None:
             src = ("choice", tuple(guided_choice))
+        elif guided_grammar is not None:
+            if not isinstance(guided_grammar, str):
+                raise TypeError(f"a grammar must be a string, got {type(guided_grammar).__name__}")
+            src = ("grammar", guided_grammar)
         else:
             src = ("json", json.dumps(guided_json, ensure_ascii=False))
         hash(src)
@@ -53,6 +60,8 @@ def _compiled_guide(cache: Dict[Any, Any], guided_regex, guided_choice, guided_j
             dfa = compile_regex(guided_regex)
         elif guided_choice is not None:
             dfa = compile_choice(list(guided_choice))
+        elif guided_grammar is not None:
+            dfa = compile_grammar(guided_grammar)
         else:
             dfa = compile_regex(schema_to_regex(guided_json))
     cache[src] = dfa                                   # (re-inserted: the most recently used is last)
@@ -260,14 +269,16 @@ class AsyncEngineCore:
                    logit_bias: Optional[Dict[int, float]] = None, prompt_logprobs: Optional[int] = None,
                    guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
                    guided_json: Optional[Dict[str, Any]] = None, beam_width: int = 0, length_penalty: float = 1.0,
-                   beam_n_best: int = 1) -> AsyncEngineCompletion:
+                   beam_n_best: int = 1, guided_grammar: Optional[str] = None) -> AsyncEngineCompletion:
         """beam_width (2..8; 0: off): beam search (DESIGN.md "Beam search") -- the request holds beam_width slots of one worker,
         streams nothing and yields one ("beams", {"hypotheses", "prompt_tokens"}) event with its beam_n_best best hypotheses, ranked by
         cumulative_logprob / max(T, 1) ** length_penalty.  It reads the raw model output: temperature, top_p, top_k, seed and the
         penalty arguments are accepted and ignored; it excludes logprobs, return_logits, prompt_logprobs, guides, logit_bias and
         forbidden_tokens, and needs stop tokens and max_tokens > 0 (ValueError).
-        guided_regex / guided_choice / guided_json (at most one): the generated text must match the pattern, be one of the strings,
-        or be compact JSON that satisfies the schema (chirrup_amd/guided.py for the subsets; GuideError, a ValueError, otherwise).  The
+        guided_regex / guided_choice / guided_json / guided_grammar (at most one): the generated text must match the pattern, be one
+        of the strings, be compact JSON that satisfies the schema, or be a text of the grammar (guided.compile_grammar: rules
+        `name ::= body` that may refer to each other and recurse, e.g. guided.JSON_OBJECT_GRAMMAR, nesting cut at 32 calls)
+        (chirrup_amd/guided.py for the subsets; GuideError, a ValueError, otherwise).  The
         request then ends "stop" exactly when its text matches; it needs stop tokens."""
         assert not (state is not None and prefill_tokens is None), "prefill_tokens cannot be None when state is not None"
         if not self.is_initialized:
@@ -277,7 +288,7 @@ class AsyncEngineCore:
         bad = [t for t in (logit_bias or {}) if isinstance(t, int) and self.vocab_size is not None and t >= self.vocab_size]
         if bad:
             raise ValueError(f"logit_bias: token id {bad[0]} is outside the vocabulary (size {self.vocab_size})")
-        guide = _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json)
+        guide = _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json, guided_grammar)
         if beam_width and self.max_choices is not None and beam_width > self.max_choices:
             raise ValueError(f"beam_width {beam_width} exceeds a worker's slot count ({self.max_choices})")
         if not prefill_tokens:
@@ -344,10 +355,10 @@ class AsyncEngineCore:
         return asyncio.ensure_future(run())
 
     def compile_guide(self, guided_regex: Optional[str] = None, guided_choice: Optional[List[str]] = None,
-                      guided_json: Optional[Dict[str, Any]] = None):
+                      guided_json: Optional[Dict[str, Any]] = None, guided_grammar: Optional[str] = None):
         """The compiled guide completion() would use for these arguments (None without any); GuideError for a bad one.  A front end
         calls it to refuse a request before it starts answering."""
-        return _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json)
+        return _compiled_guide(self._guide_cache, guided_regex, guided_choice, guided_json, guided_grammar)
 
     def completions(self, prompt_str: str, prefill_tokens: Optional[List[int]] = None, n: int = 1, **kw) -> List[AsyncEngineCompletion]:
         """n parallel choices of one prompt: completion()'s keywords, one AsyncEngineCompletion per choice (index order).  Starting

@@ -3,6 +3,8 @@
     compile_regex(pattern)   full-match regular expression over the subset below -> ByteDFA
     compile_choice(choices)  one of the given strings (built from the strings, never through regex text) -> ByteDFA
     schema_to_regex(schema)  a non-recursive JSON-Schema subset -> a pattern of the same subset (compact JSON)
+    compile_grammar(text)    rules `name ::= body` over the same patterns that may refer to each other and recurse -> StackDFA, a
+                             deterministic call/return automaton with a bounded stack (DESIGN.md "Grammar-guided decoding")
 
 The automaton runs over UTF-8 bytes: the worker walks a token's vocabulary bytes through it, so a token is allowed in a state
 exactly when its bytes keep a completion possible.  Pipeline: recursive-descent parser -> Thompson NFA whose edges are byte ranges
@@ -24,7 +26,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .core_structure import GUIDE_MAX_STATES
+from .core_structure import GUIDE_CALL_SITES_MAX, GUIDE_MAX_STATES, GUIDE_STACK_DEPTH_MAX
 
 MAX_CP = 0x10FFFF
 MAX_REPEAT = 1000                 # largest count of a {m,n}; the state bound is what really limits a pattern
@@ -327,6 +329,10 @@ class _NFA:
                         self.trans[cur].append((b0, b1, nxt))
                         cur = nxt
             return s, e
+        if kind == "call":                                  # a grammar's call of rule node[1]: one symbol past the bytes
+            s, e = self.new(), self.new()
+            self.trans[s].append((256 + node[1], 256 + node[1], e))
+            return s, e
         if kind == "cat":
             s = cur = self.new()
             for item in node[1]:
@@ -364,15 +370,15 @@ class _NFA:
         return s, e
 
 
-def _subset_construction(nfa: _NFA, start: int, final: int) -> Tuple[np.ndarray, np.ndarray]:
-    cuts = {0, 256}
+def _subset_construction(nfa: _NFA, start: int, final: int, width: int = 256) -> Tuple[np.ndarray, np.ndarray]:
+    cuts = {0, width}
     for ts in nfa.trans:
         for b0, b1, _ in ts:
             cuts.add(b0)
             cuts.add(b1 + 1)
     cuts = sorted(cuts)
     reps = cuts[:-1]                                      # one representative byte per class
-    class_of = np.zeros(256, np.int64)
+    class_of = np.zeros(width, np.int64)
     for c, (b0, b1) in enumerate(zip(cuts[:-1], cuts[1:])):
         class_of[b0:b1] = c
 
@@ -457,6 +463,12 @@ def _hopcroft(cols: np.ndarray, accept: np.ndarray, live: np.ndarray) -> Tuple[n
 
 def _finish(table: np.ndarray, accept: np.ndarray, pattern: str) -> ByteDFA:
     """A deterministic table [S, 256] (start 0, -1 dead) -> the trimmed, minimal, canonically numbered ByteDFA."""
+    return ByteDFA(*_minimise(table, accept, pattern), pattern)
+
+
+def _minimise(table: np.ndarray, accept: np.ndarray, pattern: str) -> Tuple[np.ndarray, np.ndarray]:
+    """The trimmed, minimal, canonically numbered form of a deterministic table [S, W] (start 0, -1 dead; W = 256, or wider for a
+    grammar rule, whose symbols past the bytes are its calls)."""
     S = table.shape[0]
     cols, col_of = np.unique(table, axis=1, return_inverse=True)          # byte classes: equal columns
     col_of = np.asarray(col_of).reshape(-1)
@@ -483,8 +495,8 @@ def _finish(table: np.ndarray, accept: np.ndarray, pattern: str) -> ByteDFA:
     ext = np.append(block, -1)
     q = ext[cols[rep_state]]                                              # quotient over the classes [n_blocks, C]
     # canonical numbering: breadth first from the start's block, bytes in ascending order
-    first_byte = np.full(cols.shape[1], 256, np.int64)
-    np.minimum.at(first_byte, col_of, np.arange(256))
+    first_byte = np.full(cols.shape[1], table.shape[1], np.int64)
+    np.minimum.at(first_byte, col_of, np.arange(table.shape[1]))
     class_order = np.argsort(first_byte, kind="stable")
     number = {int(block[0]): 0}
     order = [int(block[0])]
@@ -502,8 +514,7 @@ def _finish(table: np.ndarray, accept: np.ndarray, pattern: str) -> ByteDFA:
     for b, i in number.items():
         renum[b] = i
     out = renum[q[order]][:, col_of].astype(np.int32)                     # (q == -1 reads renum[-1] == -1)
-    acc = accept[rep_state[order]]
-    return ByteDFA(out, acc, pattern)
+    return out, accept[rep_state[order]]
 
 
 def token_table(idx2token: Dict[int, bytes], V: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -659,5 +670,351 @@ def schema_to_regex(schema: Dict[str, Any]) -> str:
     return _schema(schema, "schema", 0)
 
 
+# ------------------------------------------------------------------------------------------------ grammars (DESIGN.md "Grammar-guided decoding")
+_RULE_LINE = _re.compile(r"([A-Za-z_][A-Za-z0-9_]*)\s*::=(.*)$", _re.S)
+_REF = _re.compile(r"<([A-Za-z_][A-Za-z0-9_]*)>")
+_GRAMMAR_WIDTH = 256 + GUIDE_CALL_SITES_MAX               # a rule's alphabet: the bytes, then one symbol per called rule
+_NEED_INF = 255
+
+
+class _GrammarParser(_Parser):
+    """A rule body: the pattern dialect plus the atom <name> -> ("ref", name, offset)."""
+
+    def __init__(self, body: str, rule: str):
+        super().__init__(body)
+        self.rule = rule
+
+    def fail(self, what: str, at: Optional[int] = None):
+        raise GuideError(f"rule {self.rule!r}: {what} at offset {self.i if at is None else at} of its body {self.p!r}")
+
+    def atom(self):
+        if self.p[self.i] == "<":
+            m = _REF.match(self.p, self.i)
+            if m is None:
+                self.fail("'<' that opens no <rule> reference (a literal '<' is written '\\<')")
+            at, self.i = self.i, m.end()
+            return ("ref", m.group(1), at)
+        return super().atom()
+
+
+def pack_stack(stack: Sequence[int]) -> np.ndarray:
+    """A stack (call-site ids, bottom first) as the device holds it: uint64 [4], the top in the low byte of word 0, 0 below the bottom."""
+    if len(stack) > GUIDE_STACK_DEPTH_MAX or any(not 1 <= c <= GUIDE_CALL_SITES_MAX for c in stack):
+        raise GuideError(f"a stack holds at most {GUIDE_STACK_DEPTH_MAX} call sites in 1..{GUIDE_CALL_SITES_MAX}")
+    v = 0
+    for c in stack:
+        v = (v << 8) | int(c)
+    return np.array([(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)], np.uint64)
+
+
+def unpack_stack(words) -> Tuple[int, ...]:
+    """The inverse of pack_stack: the call-site ids, bottom first."""
+    v = 0
+    for k in range(4):
+        v |= (int(words[k]) & 0xFFFFFFFFFFFFFFFF) << (64 * k)
+    out = []
+    while v:
+        out.append(v & 0xFF)
+        v >>= 8
+    return tuple(reversed(out))
+
+
+class StackDFA:
+    """A deterministic call/return automaton over bytes: the minimal DFAs of the compiled rules in one state numbering (start 0).
+
+        next       int32 [S, 256]  >= 0: plain edge (the only move that consumes the byte); -1: no move of the state's own;
+                                   -(c + 1), c in 1..n_sites: call site c -- push c, go on with the same byte at site_start[c]
+        accept     bool  [S]       final state of its rule; ``called`` bool [S]: its rule is called from somewhere, so a final
+                                   state returns (pop c, go on with the same byte at site_after[c]) on a byte it has no move for
+        need       uint8 [S]       the least further stack depth a completion from the state requires
+        site_start / site_after int32 [n_sites + 1], site_need uint8 [n_sites + 1] = max(1 + need[start], need[after]); entry 0 unused
+
+    A move into a state (or through a call site) whose need exceeds the room left under max_depth is refused, so every reachable
+    (state, stack) has a completion.  The text is accepted when the returns at its end reach an accepting state with an empty
+    stack.  A stack is a tuple of call-site ids, bottom first.  ``key`` hashes all tables and max_depth.  Picklable."""
+
+    def __init__(self, next_table, accept, called, need, site_start, site_after, site_need, max_depth: int, pattern: str = ""):
+        self.next = np.ascontiguousarray(next_table, dtype=np.int32)
+        self.accept = np.ascontiguousarray(accept, dtype=np.bool_)
+        self.called = np.ascontiguousarray(called, dtype=np.bool_)
+        self.need = np.ascontiguousarray(need, dtype=np.uint8)
+        self.site_start = np.ascontiguousarray(site_start, dtype=np.int32)
+        self.site_after = np.ascontiguousarray(site_after, dtype=np.int32)
+        self.site_need = np.ascontiguousarray(site_need, dtype=np.uint8)
+        self.max_depth, self.pattern = int(max_depth), pattern
+        S, n = self.next.shape[0], self.site_start.shape[0]
+        if self.next.ndim != 2 or self.next.shape[1] != 256 or S < 1 or any(a.shape != (S,) for a in (self.accept, self.called, self.need)):
+            raise GuideError("StackDFA: next must be [S, 256] and accept, called, need [S], S >= 1")
+        if not 1 <= n <= GUIDE_CALL_SITES_MAX + 1 or self.site_after.shape != (n,) or self.site_need.shape != (n,):
+            raise GuideError(f"StackDFA: at most {GUIDE_CALL_SITES_MAX} call sites")
+        if S > GUIDE_MAX_STATES:
+            raise GuideError(f"the automaton has {S} states, more than GUIDE_MAX_STATES = {GUIDE_MAX_STATES}")
+        if not 1 <= self.max_depth <= GUIDE_STACK_DEPTH_MAX:
+            raise GuideError(f"max_depth must be in 1..{GUIDE_STACK_DEPTH_MAX}, got {max_depth}")
+        if int(self.next.min()) < -n or int(self.next.max()) >= S or (n > 1 and (
+                int(min(self.site_start[1:].min(), self.site_after[1:].min())) < 0 or int(max(self.site_start.max(), self.site_after.max())) >= S)):
+            raise GuideError("StackDFA: a transition leaves the tables")
+        h = hashlib.sha256()
+        for a in (self.next, self.accept, self.called, self.need, self.site_start, self.site_after, self.site_need):
+            h.update(a.tobytes())
+            h.update(b"|")
+        h.update(str(self.max_depth).encode())
+        self.key = h.hexdigest()
+
+    @property
+    def n_states(self) -> int:
+        return self.next.shape[0]
+
+    @property
+    def n_sites(self) -> int:
+        return self.site_start.shape[0] - 1
+
+    def edge_bytes(self) -> List[int]:
+        """The bytes that label an edge (plain, or the first byte of a call): each must be a token of the vocabulary by itself."""
+        return np.nonzero((self.next != -1).any(axis=0))[0].tolist()
+
+    def walk(self, state: int, stack: Sequence[int], data: bytes):
+        """(state, stack) after `data` from (state, stack), or None once the walk has died."""
+        st, D = list(stack), self.max_depth
+        for b in data:
+            for _ in range(2 * GUIDE_STACK_DEPTH_MAX + 2):
+                v = int(self.next[state, b])
+                if v >= 0:
+                    if len(st) + int(self.need[v]) > D:
+                        return None
+                    state = v
+                    break
+                if v < -1:
+                    c = -v - 1
+                    if len(st) + int(self.site_need[c]) > D:
+                        return None
+                    st.append(c)
+                    state = int(self.site_start[c])
+                elif st and self.accept[state] and self.called[state]:
+                    state = int(self.site_after[st.pop()])
+                else:
+                    return None
+            else:
+                return None
+        return state, tuple(st)
+
+    def ends(self, state: int, stack: Sequence[int]) -> bool:
+        """Whether the text may end at (state, stack): the returns at its end reach an accepting state with an empty stack."""
+        st = list(stack)
+        while st and self.accept[state] and self.called[state]:
+            state = int(self.site_after[st.pop()])
+        return not st and bool(self.accept[state])
+
+    def token_outcome(self, state: int, stack: Sequence[int], token_bytes: bytes):
+        """What the worker's mask decides for a token with these bytes: the (state, stack) it leads to, None when it is masked
+        (an id without bytes is always masked)."""
+        return self.walk(state, stack, token_bytes) if len(token_bytes) else None
+
+    def matches(self, text) -> bool:
+        data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        at = self.walk(0, (), data)
+        return at is not None and self.ends(*at)
+
+    def __repr__(self):
+        return (f"StackDFA({self.n_states} states, {self.n_sites} call sites, max_depth {self.max_depth}, key {self.key[:12]}, "
+                f"grammar {self.pattern[:40]!r})")
+
+
+def compile_grammar(text: str, max_depth: int = GUIDE_STACK_DEPTH_MAX) -> StackDFA:
+    """Grammar text -> StackDFA.  One rule per line, ``name ::= body``; ``#`` lines and blank lines are ignored; ``root`` is the
+    start.  A body is a pattern of the dialect above (whitespace around it stripped) plus ``<name>``, a reference to a rule (a
+    literal ``<`` is ``\\<``).  This is not GBNF: the pattern parser, its UTF-8 handling and its error offsets are reused.
+
+    Expansion policy (what max_depth counts): rules are expanded from root, depth first; a reference to a rule that is not under
+    expansion is expanded in place, a reference to a rule that is under expansion (an ancestor, or the rule itself) becomes a
+    call, and a called rule is compiled on its own by the same policy.  Each call is one push; texts that need more than max_depth
+    pushes are not members.  The grammar must be deterministic with one byte of look-ahead: every violation raises GuideError."""
+    if not isinstance(text, str):
+        raise GuideError(f"a grammar must be a string, got {type(text).__name__}")
+    if isinstance(max_depth, bool) or not isinstance(max_depth, int) or not 1 <= max_depth <= GUIDE_STACK_DEPTH_MAX:
+        raise GuideError(f"max_depth must be an integer in 1..{GUIDE_STACK_DEPTH_MAX}, got {max_depth!r}")
+    asts: Dict[str, Any] = {}
+    for ln, line in enumerate(text.split("\n"), 1):
+        line = line.strip()
+        if not line or line.startswith("#"):
+            continue
+        m = _RULE_LINE.match(line)
+        if m is None:
+            raise GuideError(f"line {ln} of the grammar is no rule 'name ::= body': {line[:60]!r}")
+        name = m.group(1)
+        if name in asts:
+            raise GuideError(f"rule {name!r} is defined twice (line {ln})")
+        asts[name] = _GrammarParser(m.group(2).strip(), name).parse()
+    if "root" not in asts:
+        raise GuideError("the grammar has no rule named 'root'")
+
+    called: Dict[str, int] = {}                            # called rule -> its symbol 256 + k, in order of the first call
+
+    budget = [0]                                           # nodes of the rule under compilation, expansions in place included
+
+    def expand(node, under: Tuple[str, ...]):
+        # expansion in place copies a rule's body at every reference, so a chain of rules can double at each link: the nodes are
+        # counted as they are made and held to the NFA's own bound (every node becomes at least one NFA state)
+        budget[0] += 1
+        if budget[0] > _NFA_MAX:
+            raise GuideError(f"rule {under[0]!r}: expanded in place (through {' -> '.join(under)}) it has more than {_NFA_MAX} nodes; "
+                             f"the grammar's references multiply its size")
+        kind = node[0]
+        if kind == "set":
+            return node
+        if kind in ("cat", "alt"):
+            return (kind, [expand(n, under) for n in node[1]])
+        if kind == "rep":
+            return ("rep", expand(node[1], under), node[2], node[3])
+        _, name, at = node
+        if name not in asts:
+            raise GuideError(f"rule {under[-1]!r}: undefined rule <{name}> at offset {at} of its body")
+        if name in under:
+            if name not in called:
+                if len(called) >= GUIDE_CALL_SITES_MAX:
+                    raise GuideError(f"rule {under[-1]!r}: more than {GUIDE_CALL_SITES_MAX} call sites (<{name}> at offset {at})")
+                called[name] = len(called)
+            return ("call", called[name])
+        return expand(asts[name], under + (name,))
+
+    # the compiled rules ("units"): root, then the called rules in order of their first call; each a minimal DFA over bytes + calls
+    units: List[str] = ["root"]
+    tables: List[Tuple[np.ndarray, np.ndarray]] = []
+    u = 0
+    while u < len(units):
+        name = units[u]
+        nfa = _NFA()
+        budget[0] = 0
+        start, final = nfa.build(expand(asts[name], (name,)))
+        t, a = _subset_construction(nfa, start, final, _GRAMMAR_WIDTH)
+        try:
+            tables.append(_minimise(t, a, f"rule {name}"))
+        except GuideError as e:
+            raise GuideError(f"rule {name!r}: {e}") from None
+        for r in sorted(called, key=called.get):
+            if r not in units:
+                units.append(r)
+        u += 1
+    base = np.cumsum([0] + [t.shape[0] for t, _ in tables])
+    S = int(base[-1])
+    if S > GUIDE_MAX_STATES:
+        raise GuideError(f"the grammar's rules have {S} states in total, more than GUIDE_MAX_STATES = {GUIDE_MAX_STATES}")
+    start_of = {name: int(base[i]) for i, name in enumerate(units)}
+    k_name = sorted(called, key=called.get)                # k -> rule
+    k_start = [start_of[r] for r in k_name]
+    plain = np.full((S, 256), -1, np.int32)
+    accept, is_called, unit_of = np.zeros(S, np.bool_), np.zeros(S, np.bool_), np.zeros(S, np.int64)
+    calls: List[List[Tuple[int, int]]] = [[] for _ in range(S)]          # per state: (k, state after the call)
+    for i, (t, a) in enumerate(tables):
+        lo, hi = int(base[i]), int(base[i + 1])
+        plain[lo:hi] = np.where(t[:, :256] >= 0, t[:, :256] + lo, -1)
+        accept[lo:hi], is_called[lo:hi], unit_of[lo:hi] = a, units[i] in called, i
+        for s, k in zip(*np.nonzero(t[:, 256:] >= 0)):
+            calls[lo + int(s)].append((int(k), lo + int(t[s, 256 + k])))
+    where = lambda s: f"rule {units[int(unit_of[s])]!r} (state {s - int(base[unit_of[s]])} of its automaton)"
+    for k, r in enumerate(k_name):
+        if accept[k_start[k]]:
+            raise GuideError(f"rule {r!r} is called and matches the empty text: a call must consume a byte")
+
+    # need, level by level: the states that complete with L further pushes, backwards from the final states
+    src, b = np.nonzero(plain >= 0)
+    rev: List[set] = [set() for _ in range(S)]
+    for s_, t_ in set(zip(src.tolist(), plain[src, b].tolist())):
+        rev[t_].add(s_)
+    need = np.full(S, _NEED_INF, np.int64)
+    for level in range(len(k_name) + 2):
+        ok = need <= level
+        ok |= accept
+        stack_ = list(np.nonzero(ok)[0])
+        call_in: List[List[int]] = [[] for _ in range(S)]               # after-state -> callers whose callee fits the level
+        for s_ in range(S):
+            for k, t_ in calls[s_]:
+                if level >= 1 and need[k_start[k]] <= level - 1:
+                    call_in[t_].append(s_)
+        while stack_:
+            t_ = int(stack_.pop())
+            for s_ in list(rev[t_]) + call_in[t_]:
+                if not ok[s_]:
+                    ok[s_] = True
+                    stack_.append(s_)
+        need[ok & (need == _NEED_INF)] = level
+    if (need == _NEED_INF).any():
+        s_ = int(np.nonzero(need == _NEED_INF)[0][0])
+        raise GuideError(f"{where(s_)} has no completion: a rule it calls matches nothing (a recursion without a way out)")
+    if need[0] > max_depth:
+        raise GuideError(f"the grammar matches nothing within max_depth = {max_depth}: its shortest text needs {int(need[0])} pushes")
+
+    # FIRST of the called rules (left recursion is a cycle among the calls made at a start state)
+    first: List[Optional[np.ndarray]] = [None] * len(k_name)
+    visiting: List[int] = []
+
+    def first_of(k: int) -> np.ndarray:
+        if first[k] is not None:
+            return first[k]
+        if k in visiting:
+            cyc = " -> ".join(k_name[j] for j in visiting[visiting.index(k):] + [k])
+            raise GuideError(f"rule {k_name[k]!r} is left recursive: it can call itself before a byte is consumed ({cyc})")
+        visiting.append(k)
+        f = plain[k_start[k]] >= 0
+        for j, _ in calls[k_start[k]]:
+            f = f | first_of(j)
+        visiting.pop()
+        first[k] = f
+        return f
+
+    for k in range(len(k_name)):
+        first_of(k)
+    # call sites and the edge table: a byte is claimed once per state
+    site_of: Dict[Tuple[int, int], int] = {}
+    site_start, site_after, site_need = [0], [0], [0]
+    nxt = plain.copy()
+    for s_ in range(S):
+        for k, t_ in calls[s_]:
+            c = site_of.get((k, t_))
+            if c is None:
+                if len(site_of) >= GUIDE_CALL_SITES_MAX:
+                    raise GuideError(f"{where(s_)}: the grammar has more than {GUIDE_CALL_SITES_MAX} call sites")
+                c = site_of[(k, t_)] = len(site_of) + 1
+                site_start.append(k_start[k])
+                site_after.append(t_)
+                site_need.append(max(1 + int(need[k_start[k]]), int(need[t_])))
+            clash = first[k] & (nxt[s_] != -1)
+            if clash.any():
+                bb = int(np.nonzero(clash)[0][0])
+                other = "a plain edge" if nxt[s_, bb] >= 0 else f"a call of <{k_name[k_start.index(site_start[-int(nxt[s_, bb]) - 1])]}>"
+                raise GuideError(f"{where(s_)}: the byte {bytes([bb])!r} is claimed twice, by {other} and by a call of <{k_name[k]}>")
+            nxt[s_, first[k]] = -(c + 1)
+    claimed = nxt != -1
+    # FOLLOW of the called rules, to a fixed point; a final state of a called rule must not claim a byte that may follow the rule
+    follow = np.zeros((len(k_name), 256), np.bool_)
+    unit_k = [called.get(name, -1) for name in units]
+    changed = True
+    while changed:
+        changed = False
+        for (k, t_) in site_of:
+            f = follow[k] | claimed[t_]
+            j = unit_k[int(unit_of[t_])]
+            if accept[t_] and j >= 0:
+                f = f | follow[j]
+            if (f != follow[k]).any():
+                follow[k], changed = f, True
+    for s_ in range(S):
+        k = unit_k[int(unit_of[s_])]
+        if accept[s_] and k >= 0 and (claimed[s_] & follow[k]).any():
+            bb = int(np.nonzero(claimed[s_] & follow[k])[0][0])
+            raise GuideError(f"{where(s_)}: a final state of the called rule can take the byte {bytes([bb])!r}, which may also "
+                             f"follow the rule (FIRST/FOLLOW conflict)")
+    return StackDFA(nxt, accept, is_called, need.astype(np.uint8), site_start, site_after, site_need, max_depth, text)
+
+
+_JSON_MEMBERS = "(" + JSON_STRING + ":<value>(," + JSON_STRING + ":<value>)*)?"
+# compact JSON with an object at the top, as schema_to_regex emits it; the one recursive rule is `value`, so one level of value
+# nesting is exactly one push
+JSON_OBJECT_GRAMMAR = ("root  ::= \\{" + _JSON_MEMBERS + "\\}\n"
+                       "value ::= \\{" + _JSON_MEMBERS + "\\}|\\[(<value>(,<value>)*)?\\]|" + JSON_STRING + "|" + JSON_NUMBER
+                       + "|true|false|null\n")
+
+
+
 __all__ = ["ByteDFA", "GuideError", "compile_regex", "compile_choice", "schema_to_regex", "escape_literal", "token_table", "JSON_STRING",
-           "JSON_INTEGER", "JSON_NUMBER"]
+           "JSON_INTEGER", "JSON_NUMBER", "StackDFA", "compile_grammar", "pack_stack", "unpack_stack", "JSON_OBJECT_GRAMMAR"]

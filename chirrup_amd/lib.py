@@ -65,6 +65,10 @@ SIGNATURES = {
     "rwkv7_guide_build": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "rwkv7_guide_apply": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "rwkv7_guide_advance": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rwkv7_grammar_build": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "rwkv7_grammar_apply": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 9),
+    "rwkv7_grammar_advance": (_i, [_i, _i, _i, _i, _vp, _vp, _i] + [_vp] * 8),
+    "rwkv7_grammar_reset": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rwkv7_embed_rows": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_i, _vp, _vp, _vp]),
     "rwkv7_advance_elapsed": (_i, [_i, _i, _vp, _vp, _vp]),
     "rwkv7_copy_slot_rows": (_i, [_i, _i, _vp, _vp, _vp, _vp]),

@@ -1474,6 +1474,318 @@ def _guide_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, guide_next, gui
             guide_state[s] = st
 
 
+GRAMMAR_STACK_DEPTH = 32           # CHIRRUP_GRAMMAR_STACK_DEPTH
+GRAMMAR_META_WORDS = 8
+
+
+def grammar_guide_rows(guide, n_stop: int) -> int:
+    """Pool rows a guided.StackDFA with n_stop stop ids occupies (include/chirrup_amd.h, "Grammar-guided decoding")."""
+    return max(guide.n_states, guide.n_sites + 1, n_stop + 1)
+
+
+def grammar_guide_tables(guide, row0: int, stop_tokens):
+    """The rows of a guided.StackDFA placed at row0, as the kernels read them: (gr_next int32 [R, 256], gr_meta int32 [R, 8])."""
+    import numpy as np
+
+    S, n, stops = guide.n_states, guide.n_sites, [int(t) for t in stop_tokens]
+    R = grammar_guide_rows(guide, len(stops))
+    nxt = np.full((R, 256), -1, np.int32)
+    nxt[:S] = np.where(guide.next >= 0, guide.next + np.int32(row0), guide.next)
+    meta = np.zeros((R, GRAMMAR_META_WORDS), np.int32)
+    meta[:S, 0] = guide.accept.astype(np.int32) | (guide.called.astype(np.int32) << 1)
+    meta[:S, 1] = guide.need
+    meta[:, 2] = row0
+    meta[:, 3] = guide.max_depth
+    meta[1:n + 1, 4] = guide.site_start[1:] + row0
+    meta[1:n + 1, 5] = guide.site_after[1:] + row0
+    meta[1:n + 1, 6] = guide.site_need[1:]
+    meta[0, 7] = len(stops)
+    meta[1:len(stops) + 1, 7] = stops
+    return nxt, meta
+
+
+def _grammar_pool_shapes(gr_next, gr_meta, bitmaps, V):
+    P = gr_next.shape[0] if gr_next.dim() == 2 else -1
+    if gr_next.dtype != torch.int32 or gr_next.dim() != 2 or gr_next.shape[1] != 256 or not gr_next.is_contiguous():
+        raise _lib.ChirrupAmdError("gr_next: expected contiguous int32 [P, 256]")
+    if gr_meta.dtype != torch.int32 or tuple(gr_meta.shape) != (P, GRAMMAR_META_WORDS) or not gr_meta.is_contiguous():
+        raise _lib.ChirrupAmdError(f"gr_meta: expected contiguous int32 [P, {GRAMMAR_META_WORDS}]")
+    for b in bitmaps:
+        if b.dtype != torch.int32 or b.dim() != 2 or not b.is_contiguous() or b.shape[0] != P or b.shape[1] * 32 != V:
+            raise _lib.ChirrupAmdError("gr_allow / gr_maybe: expected contiguous int32 [P, V / 32] (the uint32 bitmap words)")
+
+
+def _grammar_slot_shapes(gr_state, gr_stack):
+    if gr_state.dtype != torch.int32 or gr_state.dim() != 1 or gr_stack.dtype != torch.int64 or not gr_stack.is_contiguous() or \
+            tuple(gr_stack.shape) != (gr_state.numel(), 4) or gr_state.numel() == 0:
+        raise _lib.ChirrupAmdError("gr_state: expected int32 [n_slots], gr_stack: contiguous int64 [n_slots, 4] (the uint64 words)")
+
+
+def grammar_build(S: int, row0: int, gr_next, gr_meta, tok_off, tok_bytes, special, gr_allow, gr_maybe) -> None:
+    """Fills the bitmap rows [row0, row0 + S) of a grammar pool (include/chirrup_amd.h: rwkv7_grammar_build): the allow bit of
+    (s, t) says that token t survives from state s under every stack, the maybe bit that the slot's stack decides.  gr_next int32
+    [P, 256] and gr_meta int32 [P, 8] hold the guide already (grammar_guide_tables); `special` are the stop ids.  V % 64 == 0.
+    CPU tensors take the numpy form (fake backends, and the reference the kernel is tested against)."""
+    V = tok_off.numel() - 1
+    _grammar_pool_shapes(gr_next, gr_meta, (gr_allow, gr_maybe), V)
+    P = gr_next.shape[0]
+    if V <= 0 or V % 64 or S < 0 or row0 < 0 or row0 + S > P or S > 65535:
+        raise _lib.ChirrupAmdError(f"grammar_build: V = {V} must be a positive multiple of 64, rows [{row0}, {row0 + S}) inside the pool of {P}")
+    if tok_off.dtype != torch.int32 or tok_bytes.dtype != torch.uint8 or special.dtype != torch.int32:
+        raise _lib.ChirrupAmdError("tok_off / special: expected int32, tok_bytes: uint8")
+    if S == 0:
+        return
+    if not gr_next.is_cuda:
+        _grammar_build_host(S, row0, gr_next, gr_meta, tok_off, tok_bytes, special, gr_allow, gr_maybe)
+        return
+    for name, t in (("gr_next", gr_next), ("gr_meta", gr_meta), ("tok_off", tok_off), ("tok_bytes", tok_bytes), ("special", special),
+                    ("gr_allow", gr_allow), ("gr_maybe", gr_maybe)):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_grammar_build(S, row0, P, V, _ptr(gr_next), _ptr(gr_meta), _ptr(tok_off), _ptr(tok_bytes), special.numel(),
+                                         _ptr(special) if special.numel() else None, _ptr(gr_allow), _ptr(gr_maybe), _stream())
+    _lib.check(rc, "rwkv7_grammar_build")
+
+
+def _grammar_build_host(S, row0, gr_next, gr_meta, tok_off, tok_bytes, special, gr_allow, gr_maybe, chunk: int = 32):
+    import numpy as np
+
+    nxt, meta, off, by = gr_next.numpy(), gr_meta.numpy(), tok_off.numpy().astype(np.int64), tok_bytes.numpy()
+    P, V = nxt.shape[0], off.shape[0] - 1
+    lens = off[1:] - off[:-1]
+    defined = np.nonzero(lens > 0)[0]
+    sp = np.array([t for t in special.tolist() if 0 <= t < V], np.int64)
+    returns = (meta[:, 0] & 3) == 3
+    needy = meta[:, 1] != 0
+    allow_out, maybe_out = gr_allow.numpy(), gr_maybe.numpy()       # views: rows are written in place
+    for s0 in range(0, S, chunk):
+        c = min(chunk, S - s0)
+        allow, maybe = np.zeros((c, V), np.bool_), np.zeros((c, V), np.bool_)
+        si = np.repeat(np.arange(c), len(defined))              # the (state, token) pairs still on plain edges
+        ti = np.tile(defined, c)
+        cur = (row0 + s0 + si).astype(np.int64)
+        pos = 0
+        while len(ti):
+            v = nxt[cur, by[off[ti] + pos]].astype(np.int64)
+            plain = (v >= 0) & (v < P)
+            room = plain & needy[np.where(plain, v, 0)]          # a plain edge into a state with need > 0
+            go = plain & ~room
+            open_ = room | (v < -1) | ((v == -1) & returns[cur])
+            maybe[si[open_], ti[open_]] = True
+            si, ti, cur = si[go], ti[go], v[go]
+            pos += 1
+            done = lens[ti] == pos
+            allow[si[done], ti[done]] = True
+            si, ti, cur = si[~done], ti[~done], cur[~done]
+        if len(sp):
+            flags = meta[row0 + s0:row0 + s0 + c, 0] & 3
+            allow[:, sp] = (flags == 1)[:, None]
+            maybe[:, sp] = (flags == 3)[:, None]
+        allow_out[row0 + s0:row0 + s0 + c] = np.packbits(allow, axis=1, bitorder="little").view("<u4").view(np.int32)
+        maybe_out[row0 + s0:row0 + s0 + c] = np.packbits(maybe, axis=1, bitorder="little").view("<u4").view(np.int32)
+
+
+def _grammar_stack_list(words) -> list:
+    """uint64 [4] (the top in the low byte of word 0) -> call-site ids, bottom first."""
+    v = 0
+    for k in range(4):
+        v |= (int(words[k]) & 0xFFFFFFFFFFFFFFFF) << (64 * k)
+    out = []
+    while v:
+        out.append(v & 0xFF)
+        v >>= 8
+    return out[::-1]
+
+
+def _grammar_stack_words(stack) -> list:
+    v = 0
+    for c in stack:
+        v = (v << 8) | c
+    words = [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+    return [w - (1 << 64) if w >= 1 << 63 else w for w in words]       # as the int64 the tensors hold
+
+
+class _GrammarHost:
+    """The walk of include/chirrup_amd.h over a pool's host arrays, from the guide of row `st`."""
+
+    def __init__(self, nxt, meta, st):
+        self.nxt, self.meta, self.P = nxt, meta, nxt.shape[0]
+        self.base = int(meta[st, 2])
+        self.depth = min(int(meta[st, 3]), GRAMMAR_STACK_DEPTH) if 0 <= self.base < self.P else -1
+
+    def site(self, c):
+        r = self.base + c
+        return r if 1 <= c <= 255 and 0 <= r < self.P else -1
+
+    def pop(self, st, stack):
+        """One return from (st, stack): the after row, or -1."""
+        sr = self.site(stack.pop())
+        if sr < 0:
+            return -1
+        st = int(self.meta[sr, 5])
+        return st if 0 <= st < self.P else -1
+
+    def walk(self, st, stack, data):
+        stack = list(stack)
+        for b in data:
+            for _ in range(2 * GRAMMAR_STACK_DEPTH + 2):
+                v = int(self.nxt[st, b])
+                if v >= 0:
+                    if v >= self.P or len(stack) + int(self.meta[v, 1]) > self.depth:
+                        return None
+                    st = v
+                    break
+                if v < -1:
+                    sr = self.site(-v - 1)
+                    if sr < 0 or len(stack) >= GRAMMAR_STACK_DEPTH or len(stack) + int(self.meta[sr, 6]) > self.depth:
+                        return None
+                    st = int(self.meta[sr, 4])
+                    if not 0 <= st < self.P:
+                        return None
+                    stack.append(-v - 1)
+                    continue
+                if not stack or (int(self.meta[st, 0]) & 3) != 3:
+                    return None
+                st = self.pop(st, stack)
+                if st < 0:
+                    return None
+            else:
+                return None
+        return st, stack
+
+    def ends(self, st, stack):
+        stack = list(stack)
+        while stack and (int(self.meta[st, 0]) & 3) == 3:
+            st = self.pop(st, stack)
+            if st < 0:
+                return False
+        return not stack and bool(int(self.meta[st, 0]) & 1)
+
+    def stops(self):
+        if self.depth < 0:
+            return []
+        k = min(max(int(self.meta[self.base, 7]), 0), self.P - 1 - self.base)
+        return [int(self.meta[self.base + 1 + j, 7]) for j in range(k)]
+
+
+def grammar_apply(logits, rows, slot_idx, gr_state, gr_stack, gr_next, gr_meta, gr_allow, gr_maybe, tok_off, tok_bytes) -> None:
+    """logits[r][t] = -inf where the grammar of r's slot forbids token t, for the listed rows r (include/chirrup_amd.h:
+    rwkv7_grammar_apply): t is allowed iff its allow bit is set in the slot's state row, or its maybe bit is set and its walk from
+    the slot's (state, stack) survives (for a stop id: the text may end there).  fp16 logits [n, V] in place; gr_stack int64
+    [n_slots, 4].  CPU tensors take the numpy form."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or not logits.is_contiguous():
+        raise _lib.ChirrupAmdError("logits: expected contiguous fp16 [n,V]")
+    n, V = logits.shape
+    if V % 32 or tok_off.numel() != V + 1 or tok_off.dtype != torch.int32 or tok_bytes.dtype != torch.uint8:
+        raise _lib.ChirrupAmdError("grammar_apply: V % 32 == 0, tok_off int32 [V + 1], tok_bytes uint8")
+    _grammar_pool_shapes(gr_next, gr_meta, (gr_allow, gr_maybe), V)
+    _grammar_slot_shapes(gr_state, gr_stack)
+    if rows.dtype != torch.int32 or (slot_idx is not None and (slot_idx.dtype != torch.int32 or slot_idx.numel() != n)):
+        raise _lib.ChirrupAmdError("rows / slot_idx: expected int32 (slot_idx with one entry per logits row)")
+    if rows.numel() == 0:
+        return
+    if not logits.is_cuda:
+        _grammar_apply_host(logits, rows, slot_idx, gr_state, gr_stack, gr_next, gr_meta, gr_allow, gr_maybe, tok_off, tok_bytes)
+        return
+    for name, t in (("logits", logits), ("rows", rows), ("gr_state", gr_state), ("gr_stack", gr_stack), ("gr_next", gr_next), ("gr_meta", gr_meta),
+                    ("gr_allow", gr_allow), ("gr_maybe", gr_maybe), ("tok_off", tok_off), ("tok_bytes", tok_bytes)) + (
+            (("slot_idx", slot_idx),) if slot_idx is not None else ()):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_grammar_apply(rows.numel(), n, V, gr_next.shape[0], _ptr(logits), _ptr(rows), _ptr(slot_idx), gr_state.numel(),
+                                         _ptr(gr_state), _ptr(gr_stack), _ptr(gr_next), _ptr(gr_meta), _ptr(gr_allow), _ptr(gr_maybe),
+                                         _ptr(tok_off), _ptr(tok_bytes), _stream())
+    _lib.check(rc, "rwkv7_grammar_apply")
+
+
+def _grammar_apply_host(logits, rows, slot_idx, gr_state, gr_stack, gr_next, gr_meta, gr_allow, gr_maybe, tok_off, tok_bytes):
+    import numpy as np
+
+    n, V = logits.shape
+    lg, nxt, meta, P = logits.numpy().view(np.uint16), gr_next.numpy(), gr_meta.numpy(), gr_next.shape[0]
+    off, by, stacks = tok_off.tolist(), tok_bytes.numpy(), gr_stack.numpy()
+    slots = slot_idx.tolist() if slot_idx is not None else list(range(n))
+    for r in rows.tolist():
+        if not 0 <= r < n or not 0 <= slots[r] < gr_state.numel():
+            continue
+        st = int(gr_state[slots[r]])
+        if not 0 <= st < P:
+            continue
+        bits = np.unpackbits(gr_allow.numpy()[st].view(np.uint8), bitorder="little")[:V].astype(np.bool_)
+        open_ = np.unpackbits(gr_maybe.numpy()[st].view(np.uint8), bitorder="little")[:V].astype(np.bool_) & ~bits
+        g = _GrammarHost(nxt, meta, st)
+        stack, stops = _grammar_stack_list(stacks[slots[r]]), g.stops()
+        first = {}                                          # first byte -> whether it survives alone (most open tokens die on it)
+        for t in np.nonzero(open_)[0].tolist():
+            if t in stops:
+                bits[t] = g.ends(st, stack)
+            elif off[t + 1] > off[t]:
+                b = int(by[off[t]])
+                if b not in first:
+                    first[b] = g.walk(st, stack, [b]) is not None
+                bits[t] = first[b] and g.walk(st, stack, by[off[t]:off[t + 1]].tolist()) is not None
+        lg[r][~bits] = 0xFC00                               # binary16 -inf
+
+
+def grammar_advance(rows, slot_idx, ids, tok_off, tok_bytes, gr_next, gr_meta, gr_state, gr_stack) -> None:
+    """Moves state and stack of the listed rows' slots by the sampled ids (include/chirrup_amd.h: rwkv7_grammar_advance); both are
+    left as they are when the slot has no grammar (-1), the walk dies, or the id has no bytes / is outside the vocabulary."""
+    V = tok_off.numel() - 1
+    _grammar_pool_shapes(gr_next, gr_meta, (), V)
+    _grammar_slot_shapes(gr_state, gr_stack)
+    if any(t.dtype != torch.int32 for t in (rows, ids, tok_off)) or tok_bytes.dtype != torch.uint8 or (
+            slot_idx is not None and (slot_idx.dtype != torch.int32 or slot_idx.numel() != ids.numel())):
+        raise _lib.ChirrupAmdError("rows / slot_idx / ids / tok_off: expected int32 (slot_idx with one entry per id), tok_bytes: uint8")
+    if rows.numel() == 0:
+        return
+    if not gr_next.is_cuda:
+        _grammar_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, gr_next, gr_meta, gr_state, gr_stack)
+        return
+    for name, t in (("rows", rows), ("ids", ids), ("tok_off", tok_off), ("tok_bytes", tok_bytes), ("gr_next", gr_next), ("gr_meta", gr_meta),
+                    ("gr_state", gr_state), ("gr_stack", gr_stack)) + ((("slot_idx", slot_idx),) if slot_idx is not None else ()):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_grammar_advance(rows.numel(), ids.numel(), V, gr_next.shape[0], _ptr(rows), _ptr(slot_idx), gr_state.numel(),
+                                           _ptr(ids), _ptr(tok_off), _ptr(tok_bytes), _ptr(gr_next), _ptr(gr_meta), _ptr(gr_state),
+                                           _ptr(gr_stack), _stream())
+    _lib.check(rc, "rwkv7_grammar_advance")
+
+
+def _grammar_advance_host(rows, slot_idx, ids, tok_off, tok_bytes, gr_next, gr_meta, gr_state, gr_stack):
+    off, by, V, P = tok_off.tolist(), tok_bytes.numpy(), tok_off.numel() - 1, gr_next.shape[0]
+    nxt, meta, stacks = gr_next.numpy(), gr_meta.numpy(), gr_stack.numpy()
+    id_list = ids.tolist()
+    slots = slot_idx.tolist() if slot_idx is not None else list(range(len(id_list)))
+    for r in rows.tolist():
+        if not 0 <= r < len(id_list) or not 0 <= slots[r] < gr_state.numel():
+            continue
+        s, t = slots[r], id_list[r]
+        st = int(gr_state[s])
+        if not 0 <= st < P or not 0 <= t < V or off[t + 1] <= off[t]:
+            continue
+        at = _GrammarHost(nxt, meta, st).walk(st, _grammar_stack_list(stacks[s]), by[off[t]:off[t + 1]].tolist())
+        if at is not None:
+            gr_state[s] = at[0]
+            stacks[s] = _grammar_stack_words(at[1])
+
+
+def grammar_reset(slots, start, gr_state, gr_stack) -> None:
+    """gr_state[slots[i]] = start[i] (a guide's first row, or -1) with the empty stack, in stream order (include/chirrup_amd.h:
+    rwkv7_grammar_reset); slots outside the table are skipped."""
+    _grammar_slot_shapes(gr_state, gr_stack)
+    if slots.dtype != torch.int32 or start.dtype != torch.int32 or slots.numel() != start.numel():
+        raise _lib.ChirrupAmdError("slots / start: expected int32 of one length")
+    if slots.numel() == 0:
+        return
+    if not gr_state.is_cuda:
+        for s, v in zip(slots.tolist(), start.tolist()):
+            if 0 <= s < gr_state.numel():
+                gr_state[s] = v
+                gr_stack[s] = 0
+        return
+    for name, t in (("slots", slots), ("start", start), ("gr_state", gr_state), ("gr_stack", gr_stack)):
+        _chk(t, name, t.dtype)
+    rc = _lib.load().rwkv7_grammar_reset(slots.numel(), gr_state.numel(), _ptr(slots), _ptr(start), _ptr(gr_state), _ptr(gr_stack), _stream())
+    _lib.check(rc, "rwkv7_grammar_reset")
+
+
 def pool_rows(xo, seq, t0, slot, acc_sum, acc_last, acc_count) -> None:
     """Pools the ln_out rows of a chunk per sequence for text embeddings (include/chirrup_amd.h: rwkv7_pool_rows): for i, with
     b = seq[i], s = slot[i], a = t0[i]: acc_sum[s] += xo[b][a..T-1] in binary32, strictly in token order; acc_last[s] = xo[b][T-1]

@@ -55,7 +55,7 @@ def _check_logit_bias(logit_bias: Optional[Dict[str, float]]) -> None:
 
 
 def guided_arguments(engine, request, thinking: bool = False) -> Dict[str, Any]:
-    """The guided_* keywords of engine.completion() for a request's guided_regex / guided_choice / response_format, checked and
+    """The guided_* keywords of engine.completion() for a request's guided_regex / guided_choice / guided_grammar / response_format, checked and
     compiled now: every refusal is a 400 with the reason (more than one of them, json_object, a pattern or schema outside the
     supported subset, a guide on a model variant that opens with a reasoning block)."""
     kw: Dict[str, Any] = {}
@@ -73,6 +73,11 @@ def guided_arguments(engine, request, thinking: bool = False) -> Dict[str, Any]:
             raise HTTPException(status_code=400, detail="response_format: expected {\"type\": \"text\"} or {\"type\": \"json_schema\", "
                                 "\"json_schema\": {\"schema\": {...}}}")
         kw["guided_json"] = schema
+    if request.guided_grammar is not None:
+        kw["guided_grammar"] = request.guided_grammar
+        if len(kw) > 1:
+            raise HTTPException(status_code=400, detail="at most one of guided_regex, guided_choice, guided_grammar and response_format "
+                                f"json_schema may be given, got {len(kw)}")
     if len(kw) > 1:
         raise HTTPException(status_code=400, detail=f"at most one of guided_regex, guided_choice and response_format json_schema may be given, got {len(kw)}")
     if kw and thinking:
@@ -98,6 +103,7 @@ def beam_arguments(engine, request, logprobs: bool, thinking: bool = False, n: i
     conflicts = [name for name, on in (("stream", request.stream), ("logprobs", logprobs), ("logit_bias", bool(request.logit_bias)),
                                        ("guided_regex", request.guided_regex is not None),
                                        ("guided_choice", request.guided_choice is not None),
+                                       ("guided_grammar", request.guided_grammar is not None),
                                        ("response_format", request.response_format is not None
                                         and request.response_format.get("type") != "text"),
                                        ("max_tokens = 0", request.max_tokens == 0),
@@ -153,6 +159,7 @@ class ChatCompletionRequest(BaseModel):                      # api_model.py:14-6
     # other open servers), or OpenAI's response_format {"type": "json_schema", "json_schema": {"schema": {...}}}
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
+    guided_grammar: Optional[str] = None        # rules `name ::= body` (guided.compile_grammar); may recurse, e.g. guided.JSON_OBJECT_GRAMMAR
     response_format: Optional[Dict[str, Any]] = None
     # beam search (extension fields, as in other open servers): use_beam_search turns it on with beam_width beams (2..8, default 4)
     # and length_penalty; the request is not sampled -- temperature, top_p, seed and the penalties are accepted and ignored -- and
@@ -202,6 +209,7 @@ class CompletionRequest(BaseModel):
     best_of: Optional[int] = None
     guided_regex: Optional[str] = None
     guided_choice: Optional[List[str]] = None
+    guided_grammar: Optional[str] = None        # rules `name ::= body` (guided.compile_grammar); may recurse, e.g. guided.JSON_OBJECT_GRAMMAR
     response_format: Optional[Dict[str, Any]] = None
     # beam search (extension fields, as in other open servers): use_beam_search turns it on with beam_width beams (2..8, default 4)
     # and length_penalty; the request is not sampled -- temperature, top_p, seed and the penalties are accepted and ignored -- and

@@ -46,7 +46,7 @@ import torch
 from . import ops
 from .core_structure import LOGIT_BIAS_MAX, ModelLoadConfig, RequestStatus, Task
 from .embeddings import finish as finish_embedding
-from .guided import GuideError, token_table
+from .guided import GuideError, StackDFA, token_table
 from .samplers import is_greedy_row, sample_inverse_cdf, sample_logits_rwkv_pip_compatible
 
 
@@ -168,11 +168,76 @@ class GuidePool:
             e["refs"] -= 1
 
 
+class GrammarPool:
+    """The grammar guides of one worker (DESIGN.md "Grammar-guided decoding"): a pool of its own beside GuidePool, with the same
+    placement, cache key (guide.key, the sorted stop tokens), reference counts and LRU eviction.  A guide is a contiguous range of
+    rows of ``next`` int32 [P, 256], ``meta`` int32 [P, 8] and the bitmaps ``allow`` / ``maybe`` int32 [P, V/32] (layout:
+    include/chirrup_amd.h); ``state`` int32 [slots] is each slot's current row (-1: no grammar) and ``stack`` int64 [slots, 4] its
+    call stack."""
+
+    def __init__(self, rows: int, n_slots: int, V: int, device, idx2token):
+        if V % 64:
+            raise GuideError(f"guided decoding needs a vocabulary size that is a multiple of 64, got {V}")
+        if not idx2token:
+            raise GuideError("guided decoding needs the tokenizer's byte table (idx2token)")
+        off, data = token_table(idx2token, V)
+        self.single = {b[0] for i, b in idx2token.items() if 0 <= i < V and len(b) == 1}     # the bytes that are tokens by themselves
+        self.P, self.V, self.device = int(rows), V, device
+        self.tok_off, self.tok_bytes = torch.from_numpy(off).to(device), torch.from_numpy(data).to(device)
+        self.next = torch.full((self.P, 256), -1, dtype=torch.int32, device=device)
+        self.meta = torch.full((self.P, ops.GRAMMAR_META_WORDS), -1, dtype=torch.int32, device=device)
+        self.allow = torch.zeros((self.P, V // 32), dtype=torch.int32, device=device)
+        self.maybe = torch.zeros((self.P, V // 32), dtype=torch.int32, device=device)
+        self.state = torch.full((n_slots,), -1, dtype=torch.int32, device=device)
+        self.stack = torch.zeros((n_slots, 4), dtype=torch.int64, device=device)
+        self.entries: Dict[tuple, dict] = {}          # key -> {"row0", "S" (rows held), "refs", "tick"}
+        self._tick = 0
+        self.builds = 0
+
+    _place = GuidePool._place
+    release = GuidePool.release
+
+    def acquire(self, guide, stop_tokens) -> Tuple[tuple, int]:
+        """(cache key, start row) of the grammar for a request with these stop tokens, built when it is new; the caller holds one
+        reference until release(key).  GuideError when it cannot be placed or the vocabulary cannot spell it: with every byte
+        that labels an edge a token by itself, and the compiler's depth accounting, a guided row always has an allowed token."""
+        key = (guide.key, tuple(sorted(int(t) for t in stop_tokens)))
+        self._tick += 1
+        e = self.entries.get(key)
+        if e is not None:
+            e["refs"] += 1
+            e["tick"] = self._tick
+            return key, e["row0"]
+        missing = [b for b in guide.edge_bytes() if b not in self.single]
+        if missing:
+            raise GuideError(f"the vocabulary cannot realise the grammar: the byte {bytes(missing[:1])!r} labels an edge of its automaton "
+                             f"and is no token by itself ({len(missing)} such bytes)")
+        R = ops.grammar_guide_rows(guide, len(key[1]))
+        row0 = self._place(R)
+        while row0 is None:
+            idle = [k for k, v in self.entries.items() if v["refs"] == 0]
+            if not idle:
+                raise GuideError(f"the grammar pool ({self.P} rows) has no room for a guide of {R} rows: "
+                                 f"{sum(v['S'] for v in self.entries.values())} rows are held by running requests")
+            del self.entries[min(idle, key=lambda k: self.entries[k]["tick"])]
+            row0 = self._place(R)
+        # stream-ordered writes: rows of a dropped guide may still be read by a run-ahead row in flight, which runs first
+        nxt, meta = ops.grammar_guide_tables(guide, row0, key[1])
+        self.next[row0:row0 + R] = torch.from_numpy(nxt).to(self.device)
+        self.meta[row0:row0 + R] = torch.from_numpy(meta).to(self.device)
+        special = torch.tensor(key[1], dtype=torch.int32).to(self.device)
+        ops.grammar_build(guide.n_states, row0, self.next, self.meta, self.tok_off, self.tok_bytes, special, self.allow, self.maybe)
+        self.builds += 1
+        self.entries[key] = {"row0": row0, "S": R, "refs": 1, "tick": self._tick}
+        return key, row0
+
+
 class Worker:
     def __init__(self, worker_id: str, gpu_id: List[int], model_config: ModelLoadConfig, task_queue: queue.Queue,
                  master_event_queue: queue.Queue, worker_event_queue: Optional[queue.Queue], batch_size: int = 32,
                  model=None, tokenizer=None, penalize_argmax=None, state_cache_device=None, run_ahead: bool = True,
-                 state_arena=None, state_arena_rows: int = 0, peer_arenas=None, guide_pool_rows: int = 16384):
+                 state_arena=None, state_arena_rows: int = 0, peer_arenas=None, guide_pool_rows: int = 16384,
+                 grammar_pool_rows: int = 2048):
         self.worker_id, self.gpu_id, self.model_config = worker_id, gpu_id, model_config
         self.task_queue, self.master_event_queue, self.worker_event_queue = task_queue, master_event_queue, worker_event_queue
         self.real_state_size = batch_size
@@ -221,6 +286,12 @@ class Worker:
         self._guides: Optional[GuidePool] = None
         self._guide_refs: Dict[int, tuple] = {}
         self._guided = [False] * batch_size
+        # grammar guides (guided.StackDFA) have a pool of their own, allocated when the first grammar request arrives; _grammared: the
+        # slots whose row in it is not -1.  A slot is in at most one of _guided / _grammared
+        self.grammar_pool_rows = int(grammar_pool_rows)
+        self._grammars: Optional[GrammarPool] = None
+        self._grammared = [False] * batch_size
+        self._grammar_resets: Dict[int, int] = {}     # slot -> start row (or -1) written since the last forward: one reset launch
         # text embeddings (DESIGN.md "Embeddings"): per-slot accumulators (sum fp32 [n, C], last row fp16 [n, C], rows int32 [n]) that
         # ops.pool_rows fills chunk by chunk, allocated when the first embedding request arrives; _emb_host: two sets of pinned host
         # copies (the loop runs one forward ahead of the host), _emb_downloads picks the set
@@ -586,14 +657,11 @@ class Worker:
             return True
         taken = []
         try:
-            if self._guides is None:
-                self._guides = GuidePool(self.guide_pool_rows, self.real_state_size, self.model_config.vocab_size, self.device,
-                                         getattr(self.tokenizer, "idx2token", None))
             for t in group:
-                taken.append((t, self._guides.acquire(t.guide, t.stop_tokens)))
+                taken.append((t, self._pool_for(t.guide).acquire(t.guide, t.stop_tokens)))
         except GuideError as exc:
-            for _, (key, _) in taken:
-                self._guides.release(key)
+            for t, (key, _) in taken:
+                self._pool_for(t.guide).release(key)
             for t in [task] + task.siblings:
                 t.error = f"guided decoding: {exc}"
             task.request_status = RequestStatus.FINISHED_ABORTED
@@ -604,10 +672,23 @@ class Worker:
             self._guide_refs[id(t)] = ref
         return True
 
+    def _pool_for(self, guide):
+        """The pool of this kind of guide (a StackDFA goes to the grammar pool), allocated on first use."""
+        grammar = isinstance(guide, StackDFA)
+        pool = self._grammars if grammar else self._guides
+        if pool is None:
+            pool = (GrammarPool if grammar else GuidePool)(self.grammar_pool_rows if grammar else self.guide_pool_rows, self.real_state_size,
+                                                           self.model_config.vocab_size, self.device, getattr(self.tokenizer, "idx2token", None))
+            if grammar:
+                self._grammars = pool
+            else:
+                self._guides = pool
+        return pool
+
     def _release_guide(self, task: Task) -> None:
         ref = self._guide_refs.pop(id(task), None)
         if ref is not None:
-            self._guides.release(ref[0])
+            self._pool_for(task.guide).release(ref[0])
 
     def _process_accomplished_tasks(self, slots):
         for s in slots:
@@ -982,9 +1063,13 @@ class Worker:
             self.bias_counts[slot] = n_bias
             self._bias_n[slot] = n_bias
         ref = self._guide_refs.get(id(task))
-        if ref is not None or self._guided[slot]:
-            self._guides.state[slot] = ref[1] if ref is not None else -1      # the guide's start row
-            self._guided[slot] = ref is not None
+        grammar = ref is not None and isinstance(task.guide, StackDFA)
+        if (ref is not None and not grammar) or self._guided[slot]:
+            self._guides.state[slot] = ref[1] if ref is not None and not grammar else -1      # the guide's start row
+            self._guided[slot] = ref is not None and not grammar
+        if grammar or self._grammared[slot]:               # start row and empty stack (-1: the slot's previous request had a grammar):
+            self._grammar_resets[slot] = ref[1] if grammar else -1      # one launch for all of them, in front of the next forward
+            self._grammared[slot] = grammar
 
     def _organize_batch(self):
         """Slot ids per category, in slot order (the reference returns contiguous ranges after
@@ -1013,6 +1098,11 @@ class Worker:
         slots = decode_slots + prefill_slots
         if not slots:
             return None
+        if self._grammar_resets:                           # the slots admitted or forked since the last forward (a group of choices: all
+            pending, self._grammar_resets = self._grammar_resets, {}     # at once); in stream order behind the last step's advance
+            ops.grammar_reset(torch.tensor(list(pending), dtype=torch.int32).to(self.device),
+                              torch.tensor(list(pending.values()), dtype=torch.int32).to(self.device),
+                              self._grammars.state, self._grammars.stack)
         idx = self._slot_tensor(slots)
         nd = len(decode_slots)
         # every small host->device tensor is created BEFORE the forward is enqueued: a pageable H2D copy is
@@ -1030,6 +1120,8 @@ class Worker:
         lp_rows = [j for j, s in enumerate(decode_slots) if self.state_slot[s]["task"].logprobs]
         g_rows = [j for j, s in enumerate(decode_slots) if self._guided[s]]
         g_idx = self._slot_tensor(g_rows) if g_rows else None
+        s_rows = [j for j, s in enumerate(decode_slots) if self._grammared[s]]
+        s_idx = self._slot_tensor(s_rows) if s_rows else None
         # single-token prefill rows that ask for prompt logprobs: their row list and targets, uploaded before the forward
         p_asks = [(nd + j, s) for j, s in enumerate(prefill_slots) if self.state_slot[s]["plp_prompt"] is not None]
         if p_asks:
@@ -1090,6 +1182,9 @@ class Worker:
             ops.apply_logit_bias(logits, didx, self.bias_counts, self.bias_ids, self.bias_values)
         if g_rows:                                         # after the bias (a bias cannot re-admit a token), before the penalties
             ops.guide_apply(logits, g_idx, didx, self._guides.state, self._guides.allow)
+        if s_rows:                                         # the rows under a grammar, in the same place
+            G = self._grammars
+            ops.grammar_apply(logits, s_idx, didx, G.state, G.stack, G.next, G.meta, G.allow, G.maybe, G.tok_off, G.tok_bytes)
         # penalties for every decode row + arg-max, one kernel; occurrence is decayed in place
         status_out = None
         if self._commit_kernel is not None and self.device.type == "cuda":
@@ -1126,6 +1221,9 @@ class Worker:
             ops.beam_copy_states(self.batch_state, bout[:, ops.BEAM_OUT_COPY:ops.BEAM_OUT_COPY + ops.BEAM_MAX_W], b_dst)
         if g_rows:                                         # the sampled ids move the guided slots' states, on the device
             ops.guide_advance(g_idx, didx, ids, self._guides.tok_off, self._guides.tok_bytes, self._guides.next, self._guides.state)
+        if s_rows:                                         # ... and the grammar slots' states and stacks
+            G = self._grammars
+            ops.grammar_advance(s_idx, didx, ids, G.tok_off, G.tok_bytes, G.next, G.meta, G.state, G.stack)
         lp = None
         if lp_rows:                                         # the sampled ids are read on the device, in place
             lp_val, lp_ids = ops.token_logprobs(snap, lp_k, targets=ids, target_rows=lp_idx)
@@ -1378,4 +1476,4 @@ def model_load_config_for(model_path: str, vocab_path: str, vocab_size: int = 65
     return ModelLoadConfig(model_path=model_path, vocab_path=vocab_path, vocab_size=vocab_size, head_size=64)
 
 
-__all__ = ["Worker", "GuidePool", "StateCategory", "min_swaps_to_target_fast", "types"]
+__all__ = ["Worker", "GuidePool", "GrammarPool", "StateCategory", "min_swaps_to_target_fast", "types"]

@@ -565,6 +565,59 @@ int rwkv7_guide_advance(int n_rows, int n_ids, int V, int P, const int32_t *rows
                         int32_t *guide_state, void *stream);
 
 /*
+ * Grammar-guided decoding (chirrup_amd/guided.py: compile_grammar / StackDFA, DESIGN.md "Grammar-guided decoding"): a guide is a
+ * deterministic call/return automaton over bytes, a slot's constraint a state row and a stack of call sites.  The grammar guides
+ * of a worker share a pool of P rows of their own; a guide with S states, n call sites and k stop ids occupies
+ * R = max(S, n + 1, k + 1) consecutive rows from its base row0, its states first:
+ *
+ *   gr_next  int32  [P][256]  row of a state: >= 0 a plain edge to an absolute pool row (the only move that consumes the byte),
+ *                             -1 no move of the state's own, -(c + 1) for 1 <= c <= n: call site c (push c, go on with the same
+ *                             byte at the site's start row)
+ *   gr_meta  int32  [P][8]    words 0..3 describe the row as a state: flags (bit 0 final state of its rule, bit 1 its rule is
+ *                             called, so a final state returns: pop c, go on with the same byte at site c's after row), need (the
+ *                             least further stack depth a completion requires), row0 of its guide, the guide's depth bound
+ *                             (1..CHIRRUP_GRAMMAR_STACK_DEPTH).  Words 4..6 of row row0 + c are call site c of the guide: start
+ *                             row, after row (absolute), need = max(1 + need[start], need[after]).  Word 7 of row row0 is k, of
+ *                             row row0 + 1 + j the j-th stop id.
+ *   gr_allow, gr_maybe uint32 [P][V/32]  bit t of a state's row: token t is allowed under every stack / under some stacks only
+ *   gr_state int32  [n_slots]      a slot's current row, -1 for a slot without a grammar
+ *   gr_stack uint64 [n_slots][4]   32 call-site bytes, the top in the low byte of word 0, zero above the bottom (the depth is the
+ *                                  number of non-zero bytes)
+ *
+ * A walk of bytes from (row, stack, depth d) takes, per byte: the plain edge to row v when d + need[v] <= bound; else the call
+ * site c when d + need[c] <= bound and d < CHIRRUP_GRAMMAR_STACK_DEPTH; else, from a final state of a called rule with d > 0, the
+ * return; else it dies.  The text may end where the returns reach a final state with d == 0.  A row or site outside the pool met
+ * anywhere counts as dead.  The token byte table (tok_off, tok_bytes) is that of rwkv7_guide_build.
+ *
+ * rwkv7_grammar_build fills gr_allow / gr_maybe rows [row0, row0 + S) (V % 64 == 0, both 8-byte aligned; gr_next / gr_meta rows
+ * of the guide already written, stream order): the allow bit of (s, t) is set iff t has bytes and all of them take plain edges
+ * into rows with need == 0; the maybe bit iff allow is clear and the first byte that does not is a plain edge into a row with
+ * need > 0, a call, or has no move in a final state of a called rule.  For the n_special stop ids the bits are instead
+ * allow = final && !called, maybe = final && called of row row0 + s.
+ *
+ * rwkv7_grammar_apply: as rwkv7_guide_apply, with token t allowed iff its allow bit is set, or its maybe bit is set and its walk
+ * from the slot's (row, stack) survives -- for a stop id of the guide, iff the text may end there.
+ *
+ * rwkv7_grammar_advance: as rwkv7_guide_advance; the walk of ids[r]'s bytes moves gr_state[s] and gr_stack[s], or leaves both
+ * when it dies.  rwkv7_grammar_reset: for i < n, gr_state[slots[i]] = start[i] (a guide's row0, or -1) and the stack is emptied;
+ * slots outside [0, n_slots) are skipped.
+ */
+#define CHIRRUP_GRAMMAR_STACK_DEPTH 32
+#define CHIRRUP_GRAMMAR_CALL_SITES 255
+int rwkv7_grammar_build(int S, int row0, int P, int V, const int32_t *gr_next, const int32_t *gr_meta, const int32_t *tok_off,
+                        const uint8_t *tok_bytes, int n_special, const int32_t *special, uint32_t *gr_allow, uint32_t *gr_maybe,
+                        void *stream);
+int rwkv7_grammar_apply(int n_rows, int n_logit_rows, int V, int P, void *logits, const int32_t *rows, const int32_t *slot_idx,
+                        int n_slots, const int32_t *gr_state, const uint64_t *gr_stack, const int32_t *gr_next, const int32_t *gr_meta,
+                        const uint32_t *gr_allow, const uint32_t *gr_maybe, const int32_t *tok_off, const uint8_t *tok_bytes,
+                        void *stream);
+int rwkv7_grammar_advance(int n_rows, int n_ids, int V, int P, const int32_t *rows, const int32_t *slot_idx, int n_slots,
+                          const int32_t *ids, const int32_t *tok_off, const uint8_t *tok_bytes, const int32_t *gr_next,
+                          const int32_t *gr_meta, int32_t *gr_state, uint64_t *gr_stack, void *stream);
+int rwkv7_grammar_reset(int n, int n_slots, const int32_t *slots, const int32_t *start, int32_t *gr_state, uint64_t *gr_stack,
+                        void *stream);
+
+/*
  * Beam search (DESIGN.md "Beam search").  A beam group of width W (2..CHIRRUP_BEAM_MAX_W) with S stop ids (S >= 1, W + S <= 20) holds
  * W slots of the worker's state tables, one per position.  Every step, rwkv7_token_logprobs gives each position's K = W + S most likely
  * ids; rwkv7_beam_select picks the next beams of every group of the step on the device and rwkv7_beam_copy_states moves the states
