@@ -254,3 +254,86 @@ def test_layer_norm_reference_accepts_binary32_orders_and_rejects_mutants(regime
         res = R.check(cur, ref["cur"][0], ref["cur"][1], group=C)
         print(f"   one_pass_variance rejected on {res['bad']} of {res['n']}")
         assert res["bad"] >= 0.01 * res["n"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launch forms of rwkv7_add_ln_mix / _mm8 (tests/test_ln_forms_gpu.py): each form at its smallest GPU shape
+
+LN_FORMS = {
+    # name: (ln_form_inputs arguments, R, PL, the mutants this form must reject)
+    "grouped-ragged-n6": (dict(B=2, T=9, C=64, n_mix=6), 2, 8, ["group_shift_from_carry", "carry_from_last_full_group"]),
+    "grouped-ragged-n1": (dict(B=2, T=9, C=64, n_mix=1), 2, 8, ["group_shift_from_carry", "carry_from_last_full_group"]),
+    "grouped-n0": (dict(B=2, T=9, C=64, n_mix=0), 2, 8, []),
+    "grouped-1024-lanes": (dict(B=2, T=9, C=2112, n_mix=6), 2, 4, ["group_shift_from_carry", "carry_from_last_full_group"]),
+    "planes-9-of-8": (dict(B=2, T=9, C=192, n_mix=6, splits=9), 2, 8, ["planes_summed_in_binary16", "planes_beyond_PL_dropped", "delta_added_unrounded"]),
+    "planes-5-of-4": (dict(B=5, T=1, C=2112, n_mix=1, splits=5), 1, 4, ["planes_summed_in_binary16", "planes_beyond_PL_dropped", "delta_added_unrounded"]),
+    "planes-n0": (dict(B=5, T=1, C=192, n_mix=0, splits=17), 1, 8, ["planes_summed_in_binary16", "planes_beyond_PL_dropped", "delta_added_unrounded"]),
+    "mm8-in-grid": (dict(B=5, T=1, C=192, n_mix=0, splits=5, mm8_in="grid", parts=65), 1, 8,
+                    ["offset_1024", "S_parts_beyond_64_dropped", "S1_S2_swapped"]),
+    "mm8-in-real": (dict(B=5, T=1, C=192, n_mix=1, splits=5, mm8_in="real", parts=65), 1, 8,
+                    ["offset_1024", "S_parts_beyond_64_dropped", "S1_S2_swapped", "delta_added_unrounded"]),
+    "mm8-in-grid-1024-lanes": (dict(B=2, T=9, C=2112, n_mix=1, splits=5, mm8_in="grid", parts=65), 2, 4,
+                               ["offset_1024", "S_parts_beyond_64_dropped", "S1_S2_swapped", "planes_beyond_PL_dropped", "group_shift_from_carry"]),
+    "mm8-out-3": (dict(B=2, T=9, C=192, n_mix=6, out_planes=3), 2, 8, ["prologue_ry_of_plane_0", "out_S_rows_by_t"]),
+    "mm8-out-1": (dict(B=5, T=1, C=192, n_mix=1, out_planes=1), 1, 8, []),
+    "mm8-in-out": (dict(B=2, T=9, C=2112, n_mix=6, splits=5, mm8_in="real", parts=3, out_planes=2), 2, 4,
+                   ["offset_1024", "S1_S2_swapped", "prologue_ry_of_plane_0", "out_S_rows_by_t", "carry_from_last_full_group"]),
+}
+
+
+def test_every_ln_mutant_has_a_form_that_must_reject_it():
+    assert set(R.LN_MUTANTS) == {m for _, _, _, ms in LN_FORMS.values() for m in ms}
+
+
+@pytest.mark.parametrize("name", list(LN_FORMS))
+def test_ln_form_reference_accepts_binary32_orders_and_rejects_mutants(name):
+    """Each launch form: the reference accepts the emulation in two summation orders (0 elements outside) and rejects every defect
+    listed for the form.  Family "real" keeps its condition: at most 5 % of x_new with more than one candidate."""
+    kw, Rg, PL, mutants = LN_FORMS[name]
+    li = R.ln_form_inputs(seed=len(name), **kw)
+    for order in ("pairwise", "lanes"):
+        res = R.ln_form_check(li, R.ln_emulate(li, order, R=Rg, PL=PL, full=True))
+        assert res["bad"] == 0 and not res["fails"], (order, res["fails"])
+        assert res["multi"] <= 0.05                        # a condition on the inputs, computed from the reference alone
+        if kw.get("mm8_in") != "real":
+            assert res["multi"] == 0.0                     # exact forms: x_new has one admissible pattern everywhere
+    print(f"LN form {name}: {res['single']} of {res['n']} single-pattern, multi-candidate x_new {res['multi']:.5f}")
+    for mutant in mutants:
+        res = R.ln_form_check(li, R.ln_emulate(li, "lanes", mutant, R=Rg, PL=PL, full=True))
+        print(f"   {mutant} rejected on {res['bad']} of {res['n']}: {res['fails'][0][:150] if res['fails'] else ''}")
+        assert res["bad"] > 0 and res["fails"], mutant
+
+
+@pytest.mark.parametrize("C,parts,splits", [(192, 1, 1), (192, 64, 3), (2112, 65, 5), (2112, 130, 12)])
+def test_mm8_in_grid_is_exact_in_any_order(C, parts, splits):
+    """Family "grid": the part sums and the whole correction are exact in binary32 -- the same bits under two part orders, both
+    associations of the final sum and the binary64 evaluation -- and a good share of the results still needs the binary16 rounding."""
+    li = R.ln_form_inputs(3, 1, C, n_mix=0, splits=splits, mm8_in="grid", parts=parts, seed=C + parts)
+    d_lo, d_hi = R.ln_delta_interval(li)
+    assert np.array_equal(bits(d_lo), bits(d_hi))
+    f = lambda a: np.asarray(a).astype(F32)
+    acc = R.planes_sum(li["planes"])
+    perm = np.random.default_rng(1).permutation(parts)
+    S = li["in_S"]
+    seq = np.zeros((S.shape[0], 3), F32)
+    for pp in perm:
+        seq = seq + S[:, pp]
+    results = []
+    for Ssum in (S.sum(1, dtype=F32), seq, S[:, ::-1].sum(1, dtype=F32)):
+        assert np.array_equal(Ssum, S.astype(np.float64).sum(1))
+        s0, s1, s2 = (Ssum[:, None, None, k] for k in range(3))
+        core = f(li["in_rx"]) * (acc - F32(1023.5) * s0)
+        results.append(((core + s1) + f(li["in_mx"]) * s2))
+        results.append((core + (s1 + f(li["in_mx"]) * s2)))
+    for r in results:
+        assert r.dtype == F32 and np.array_equal(r, results[0])
+        assert np.array_equal(bits(r.astype(F16)), bits(d_lo))
+    rounded = float((results[0].astype(F16).astype(F32) != results[0]).mean())
+    print(f"grid C{C} parts{parts}: {rounded:.3f} of the deltas need the binary16 rounding, mean |delta| {np.abs(results[0]).mean():.3f}")
+    assert 0.1 <= rounded <= 0.9                           # the h() of delta is exercised, on inexact and on exact values alike
+
+
+def test_ln_reference_without_mix_planes_has_no_carry():
+    li = R.ln_form_inputs(2, 3, 64, n_mix=0, seed=1)
+    ref = R.ln_form_reference(li)
+    assert ref["carry"] is None and ref["out"][0].shape == (1, 2, 3, 64) and np.array_equal(bits(ref["out"][0][0]), bits(ref["cur"][0]))

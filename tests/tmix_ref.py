@@ -351,11 +351,14 @@ def from_key(kx):
 
 
 def ln_mix_reference(x, delta, w, b, prev, mix, eps=1e-5, slot_idx=None):
-    """x, delta [B,T,C] (delta may be None), prev [n_slots,C] the carry table, mix [n_mix,C] with 0 <= mix <= 1.
+    """x, delta [B,T,C] (delta may be None), prev [n_slots,C] the carry table, mix [n_mix,C] with 0 <= mix <= 1, n_mix 1 or 6, or
+    None (n_mix = 0: out is the interval of cur, one plane, and there is no carry: carry = None).
     Returns x_new (exact), cur (lo, hi, mid) [B,T,C], out (lo, hi) [n_mix,B,T,C], carry (lo, hi) [n_slots,C]."""
     B, T, C = x.shape
     xn = x if delta is None else x + delta
     c_lo, c_hi, c_mid = (a.reshape(B, T, C) for a in group_norm_interval(xn.reshape(B * T, C), w, b, eps, group=C))
+    if mix is None:
+        return dict(x_new=xn, cur=(c_lo, c_hi, c_mid), out=(c_lo[None], c_hi[None]), carry=None)
     slots = np.arange(B) if slot_idx is None else np.asarray(slot_idx)
     p0 = prev[slots][:, None]
     s_lo = np.concatenate([p0, c_lo[:, :-1]], 1)
@@ -403,37 +406,276 @@ def ln_inputs(B, T, C, regime, seed=0, n_slots=None, n_mix=6):
                 mix=rng.uniform(0, 1, (n_mix, C)).astype(F16), slot_idx=rng.permutation(n_slots)[:B].astype(np.int32))
 
 
-def ln_emulate(li, order="pairwise", mutant=None, eps=1e-5):
-    """A binary32 evaluation of add_ln_mix on ln_inputs: "pairwise" (numpy) or "lanes" (128 per-lane partial sums added in order,
-    then butterfly-free sequential combine).  mutant: "one_pass_variance" or "no_round_lerp".  Returns (out [n_mix,B,T,C], cur)."""
+# ---------------------------------------------------------------------------------------------------------------------
+# The launch forms of rwkv7_add_ln_mix / rwkv7_add_ln_mix_mm8: n_mix 0 / 1 / 6, rows grouped R to a workgroup, delta from split-K
+# planes, the mm8 correction of those planes (in_*), the mm8 prologue of the mixed planes (out_*).
+#
+#   planes    acc = ((0 + p_0) + p_1) + ...: binary32, plane order (the kernel adds the planes of a batch of PL loads in order and
+#             the batches in order; -ffp-contract=off), delta = h(acc), x_new = h(x + delta): EXACT.
+#   mm8 in_*  acc' = ((rx (acc - 1023.5 S0)) + S1) + mx S2 with S0, S1, S2 the sums of in_S_parts parts.  The inputs keep the PART
+#             sums exact in any order (S0 parts even integers, S1 parts multiples of 2^-6, S2 parts of 2^-4, all small: the
+#             exact-sum lemma), and 1023.5 S0 and mx S2 exact (asserted).  Every one of the four remaining operations contributes
+#             its rounding u |result| only where its operands are exact and its binary64 result is not a binary32 number -- so
+#             family "grid" (integer planes with acc - 1023.5 S0 an integer below 2^11, rx and |mx| powers of two) is exact from end
+#             to end, and family "real" (any rx, mx, planes) is bounded by four roundings.  delta lies between h(D - e) and
+#             h(D + e), x_new between h(x + h(D - e)) and h(x + h(D + e)) (both monotone).
+#   after     the LayerNorm / lerp intervals are computed from the x_new the evaluation under test produced (the staged check): an
+#             x_new inside its candidates with a wrong row behind it still fails.
+#   mm8 out_* xs[m] = h(out[m] ry[m]) from the produced out[m] bits: exact.  S[m][row] = {sum xs, sum out my, sum out} over C terms
+#             (the products of two halves are exact in binary32): binary64 sums, bound gamma(C) sum|terms| + SLACK in any order.
+#             Planes >= out_planes of xs and S keep their canary.
+
+CANARY = 7.0
+
+
+def _is_f32(v):
+    with np.errstate(over="ignore", invalid="ignore"):
+        return v.astype(F32).astype(F64) == v
+
+
+def ln_form_inputs(B, T, C, n_mix=6, splits=0, mm8_in=None, parts=1, out_planes=0, seed=0, regime="plain"):
+    """ln_inputs plus what selects a launch form.  splits > 0: delta comes from `planes` (binary32 [splits,B,T,C]) and li["delta"] is
+    None.  mm8_in "grid" / "real" (needs splits): the planes are core sums, with in_rx, in_mx [C] and in_S [B*T,parts,3] (see above).
+    out_planes > 0: out_ry, out_my [out_planes,C], distinct per plane."""
+    li = ln_inputs(B, T, C, regime, seed=seed, n_mix=max(n_mix, 1))
+    rng = np.random.default_rng(seed + 7919)
+    rows = B * T
+    li.update(n_mix=n_mix, planes=None, family=mm8_in, in_rx=None, in_mx=None, in_S=None, out_ry=None, out_my=None)
+    if n_mix == 0:
+        li["mix"] = None
+    if mm8_in is not None:
+        assert splits > 0 and mm8_in in ("grid", "real")
+        amp = max(1, int(round(24 / np.sqrt(parts))))
+        nz = lambda: rng.integers(1, amp + 1, (rows, parts)) * rng.choice([-1, 1], (rows, parts))     # never 0: every part counts
+        S = np.stack([2.0 * nz(), nz() * 2.0 ** -6, nz() * 2.0 ** -4], -1)
+        t = 1023.5 * S[..., 0].sum(1)[:, None]
+        if mm8_in == "grid":
+            rx = 2.0 ** -rng.integers(10, 14, C)                              # rx A: multiples of 2^-10 .. 2^-13 below 2
+            mx = rng.choice([-1.0, 1.0], C) * 2.0 ** -rng.integers(6, 9, C)        # mx S2: multiples of 2^-12, so h() rounds
+            core = t + rng.integers(-2047, 2048, (rows, C))
+            pl = rng.integers(-4096, 4097, (splits, rows, C)).astype(F64)
+        else:
+            rx = 2.0 ** -10 * rng.uniform(0.5, 2.0, C)
+            mx = 0.1 * rng.standard_normal(C)
+            core = t + 400.0 * rng.standard_normal((rows, C))
+            pl = (2000.0 * rng.standard_normal((splits, rows, C))).astype(F32).astype(F64)
+        pl[-1] = core - pl[:-1].sum(0)
+        li.update(planes=pl.astype(F32).reshape(splits, B, T, C), delta=None, in_rx=rx.astype(F16), in_mx=mx.astype(F16), in_S=S.astype(F32))
+    elif splits:
+        li.update(planes=(rng.standard_normal((splits, B, T, C)) * 0.5 / np.sqrt(splits)).astype(F32), delta=None)
+    if out_planes:
+        li.update(out_ry=rng.uniform(0.5, 2.0, (out_planes, C)).astype(F16), out_my=(0.1 * rng.standard_normal((out_planes, C))).astype(F16))
+    return li
+
+
+def planes_sum(planes, dtype=F32):
+    """((0 + p_0) + p_1) + ... in `dtype`, one rounding per addition."""
+    acc = np.zeros(planes.shape[1:], dtype)
+    for p in planes:
+        acc = (acc + p.astype(dtype)).astype(dtype)
+    return acc
+
+
+def ln_delta_interval(li):
+    """(d_lo, d_hi) binary16 [B,T,C]: the admissible deltas (equal bits: exact); (None, None) without a delta."""
+    if li["planes"] is None:
+        return li["delta"], li["delta"]
+    B, T, C = li["x"].shape
+    with np.errstate(over="ignore", invalid="ignore"):
+        acc = planes_sum(li["planes"])
+        if li["in_S"] is None:
+            return h(acc), h(acc)
+        S = li["in_S"].astype(F64)
+        q = np.array([2.0, 2.0 ** -6, 2.0 ** -4])
+        assert (S / q == np.round(S / q)).all() and (np.abs(S).sum(1) < 2.0 ** 24 * q).all(), "in_S parts off their grid: sums not exact"
+        S = S.sum(1).reshape(B, T, 1, 3)
+        S0, S1, S2 = S[..., 0], S[..., 1], S[..., 2]
+        rx, mx = li["in_rx"].astype(F64), li["in_mx"].astype(F64)
+        t, m = 1023.5 * S0, mx * S2
+        assert _is_f32(t).all() and _is_f32(m).all(), "1023.5 S0 or mx S2 rounds: more than four roundings"
+        A = acc.astype(F64) - t
+        e = np.where(_is_f32(A), 0.0, U * np.abs(A))
+        step = lambda v, e: np.where((e == 0) & _is_f32(v), 0.0, e + U * (np.abs(v) + e))      # one rounding, unless nothing rounds
+        A, e = rx * A, np.abs(rx) * e
+        e = step(A, e)
+        A = A + S1
+        e = step(A, e)
+        A = A + m
+        e = step(A, e)
+        e = e + SLACK * np.abs(A) * (e > 0)
+        return h(A - e), h(A + e)
+
+
+def ln_form_reference(li, x_out=None, eps=1e-5):
+    """The reference of one launch.  x_out: the x_new bits of the evaluation under test (needed where x_new has more than one
+    candidate: the LN intervals are then those of x_out's rows); None: the lower candidate.
+    Returns x_new (lo, hi), multi (the share of elements with more than one admissible x_new), and ln_mix_reference's cur / out /
+    carry computed from x_out."""
+    d_lo, d_hi = ln_delta_interval(li)
+    x = li["x"]
+    with np.errstate(over="ignore", invalid="ignore"):
+        x_lo, x_hi = (x, x) if d_lo is None else (x + d_lo, x + d_hi)
+    swap = key(x_lo) > key(x_hi)
+    x_lo, x_hi = np.where(swap, x_hi, x_lo), np.where(swap, x_lo, x_hi)
+    xn = x_lo if x_out is None else np.asarray(x_out).reshape(x.shape)
+    ref = ln_mix_reference(xn, None, li["w"], li["b"], li["prev"], li["mix"], eps, li["slot_idx"])
+    ref.update(x_new=(x_lo, x_hi), multi=float((bits(x_lo) != bits(x_hi)).mean()))
+    return ref
+
+
+def ln_mm8_out_reference(out, ry, my):
+    """out [P,B,T,C] known halves (the first P mixed planes), ry, my [P,C] -> xs [P,B,T,C] exact, S [P,B*T,3] binary64 and its bound."""
+    P, B, T, C = out.shape
+    with np.errstate(over="ignore", invalid="ignore"):
+        xs = out * ry[:, None, None, :]
+        o64 = out.astype(F64)
+        terms = [xs.astype(F64), o64 * my.astype(F64)[:, None, None, :], o64]
+        S = np.stack([t.reshape(P, B * T, C).sum(-1) for t in terms], -1)
+        bound = np.stack([np.abs(t).reshape(P, B * T, C).sum(-1) for t in terms], -1) * (gamma(C) + SLACK)
+    return xs, S, bound
+
+
+def ln_form_check(li, got, eps=1e-5):
+    """got: x_new [B,T,C] (absent without a delta), out [max(n_mix,1),B,T,C], carry [n_slots,C] (n_mix > 0), and with out_planes: xs
+    [3,B,T,C], S [3,B*T,3], both pre-filled with CANARY.  Returns counts: n / single / bad over x_new, the mixed planes and the carry
+    rows; multi (the share of x_new with more than one candidate); fails: one line per property that does not hold (empty: pass)."""
+    B, T, C = li["x"].shape
+    n_mix = li["n_mix"]
+    ref = ln_form_reference(li, got.get("x_new"), eps)
+    res = dict(n=0, single=0, bad=0, multi=ref["multi"], fails=[])
+
+    def add(name, r):
+        res["n"] += r["n"]
+        res["single"] += r["single"]
+        res["bad"] += r["bad"]
+        if r["bad"]:
+            res["fails"].append(f"{name}: {r['msg']}")
+
+    def same_bits(name, a, b):
+        d = int((bits(np.asarray(a)) != bits(np.asarray(b))).sum()) if np.asarray(a).dtype == F16 else int((np.asarray(a) != np.asarray(b)).sum())
+        if d:
+            res["bad"] += d
+            res["fails"].append(f"{name}: {d} of {np.asarray(a).size} elements differ")
+    if "x_new" in got:
+        add("x_new", check(got["x_new"], *ref["x_new"], group=C))
+    add("out", check(got["out"], *ref["out"], group=C))
+    if n_mix:
+        add("carry", check(got["carry"], *ref["carry"], group=C))
+        others = np.setdiff1d(np.arange(li["prev"].shape[0]), li["slot_idx"])
+        same_bits("carry rows of other slots", got["carry"][others], li["prev"][others])
+    if li["out_ry"] is not None:
+        P = li["out_ry"].shape[0]
+        xs, S, bound = ln_mm8_out_reference(np.asarray(got["out"])[:P], li["out_ry"], li["out_my"])
+        same_bits("xs", got["xs"][:P], xs)
+        with np.errstate(invalid="ignore"):
+            off = ~(np.abs(got["S"][:P].astype(F64) - S) <= bound)
+        res["n"] += off.size
+        if off.any():
+            res["bad"] += int(off.sum())
+            r = np.argwhere(off)[0]
+            res["fails"].append(f"S: {int(off.sum())} of {off.size} sums outside their bound, first [plane, row, k] = {r.tolist()}: got "
+                                f"{got['S'][tuple(r)]!r} want {S[tuple(r)]!r} +- {bound[tuple(r)]:.3g}")
+        same_bits("xs planes >= out_planes", got["xs"][P:], np.full_like(got["xs"][P:], CANARY))
+        same_bits("S planes >= out_planes", got["S"][P:], np.full_like(got["S"][P:], CANARY))
+    return res
+
+
+def ln_emulate(li, order="pairwise", mutant=None, eps=1e-5, R=1, PL=8, full=False):
+    """A binary32 evaluation of add_ln_mix on ln_inputs / ln_form_inputs.  order: "pairwise" (numpy) or "lanes" (per-lane partial sums
+    added in order, then a sequential combine; the in_S parts lane-strided by 64).  R: rows per workgroup, PL: planes per batch
+    (both only change what the mutants do).  mutant: one of LN_MUTANTS, "one_pass_variance" or "no_round_lerp".
+    Returns (out [n_mix,B,T,C], cur), or with full=True the dict ln_form_check takes."""
     f = lambda a: np.asarray(a).astype(F32)
-    x = li["x"] + li["delta"]
+    x = li["x"]
     B, T, C = x.shape
-    xf = f(x)
+    W = 128 if C % 128 == 0 else 64
 
     def rsum(a):
         if order == "pairwise":
             return a.sum(-1, keepdims=True, dtype=F32)
-        part = a.reshape(B, T, C // 128, 128)
-        acc = part[:, :, 0].copy()
-        for i in range(1, C // 128):
-            acc = acc + part[:, :, i]
+        part = a.reshape(a.shape[:-1] + (a.shape[-1] // W, W))
+        acc = part[..., 0, :].copy()
+        for i in range(1, part.shape[-2]):
+            acc = acc + part[..., i, :]
         tot = acc[..., 0].copy()
-        for j in range(1, 128):
+        for j in range(1, W):
             tot = tot + acc[..., j]
         return tot[..., None]
-    mean = rsum(xf) / F32(C)
-    d = xf - mean
-    var = rsum(xf * xf) / F32(C) - mean * mean if mutant == "one_pass_variance" else rsum(d * d) / F32(C)
-    cur = h(d * (F32(1.0) / np.sqrt(var + F32(eps))) * f(li["w"]) + f(li["b"]))
-    sh = np.concatenate([li["prev"][li["slot_idx"]][:, None], cur[:, :-1]], 1)
-    outs = []
-    for m in range(li["mix"].shape[0]):
-        dx = f(h(f(sh) - f(cur))) * f(li["mix"][m])
-        if mutant != "no_round_lerp":
-            dx = f(h(dx))
-        outs.append(h(f(cur) + dx))
-    return np.stack(outs), cur
+    got = {}
+    planes = li.get("planes")
+    with np.errstate(over="ignore", invalid="ignore"):
+        if planes is not None:
+            if mutant == "planes_beyond_PL_dropped":
+                planes = planes[:PL]
+            acc = f(planes_sum(planes, F16 if mutant == "planes_summed_in_binary16" else F32))
+            if li["in_S"] is not None:
+                Sp = li["in_S"][:, :64] if mutant == "S_parts_beyond_64_dropped" else li["in_S"]
+                if order == "pairwise":
+                    S = Sp.sum(1, dtype=F32)
+                else:
+                    lanes = np.zeros((Sp.shape[0], 64, 3), F32)
+                    for pp in range(Sp.shape[1]):
+                        lanes[:, pp % 64] = lanes[:, pp % 64] + Sp[:, pp]
+                    S = lanes[:, 0].copy()
+                    for j in range(1, 64):
+                        S = S + lanes[:, j]
+                S = S.reshape(B, T, 1, 3)
+                s0, s1, s2 = S[..., 0], S[..., 2 if mutant == "S1_S2_swapped" else 1], S[..., 1 if mutant == "S1_S2_swapped" else 2]
+                off = F32(1024.0 if mutant == "offset_1024" else 1023.5)
+                acc = f(li["in_rx"]) * (acc - off * s0) + s1 + f(li["in_mx"]) * s2
+            xn = h(f(x) + (acc if mutant == "delta_added_unrounded" else f(h(acc))))
+            got["x_new"] = xn
+        elif li["delta"] is not None:
+            xn = x + li["delta"]
+            got["x_new"] = xn
+        else:
+            xn = x
+        xf = f(xn)
+        mean = rsum(xf) / F32(C)
+        d = xf - mean
+        var = rsum(xf * xf) / F32(C) - mean * mean if mutant == "one_pass_variance" else rsum(d * d) / F32(C)
+        cur = h(d * (F32(1.0) / np.sqrt(var + F32(eps))) * f(li["w"]) + f(li["b"]))
+        mix = li["mix"]
+        if mix is None:
+            got["out"] = cur[None]
+            return got if full else (got["out"], cur)
+        p0 = li["prev"][li["slot_idx"]]
+        sh = np.concatenate([p0[:, None], cur[:, :-1]], 1)
+        if mutant == "group_shift_from_carry":                   # a group's first row (t0 > 0) shifts against the carry table
+            sh[:, R::R] = p0[:, None]
+        outs = []
+        for m in range(mix.shape[0]):
+            dx = f(h(f(sh) - f(cur))) * f(mix[m])
+            if mutant != "no_round_lerp":
+                dx = f(h(dx))
+            outs.append(h(f(cur) + dx))
+        out = np.stack(outs)
+        carry = li["prev"].copy()
+        last = (T // R) * R - 1 if mutant == "carry_from_last_full_group" and T % R and T >= R else T - 1
+        carry[li["slot_idx"]] = cur[:, last]
+        got.update(out=out, carry=carry)
+        if li.get("out_ry") is not None:
+            P = li["out_ry"].shape[0]
+            xs_all = np.full((3, B, T, C), CANARY, F16)
+            S_all = np.full((3, B * T, 3), CANARY, F32)
+            for m in range(P):
+                ry = li["out_ry"][0 if mutant == "prologue_ry_of_plane_0" else m]
+                xs = h(f(out[m]) * f(ry))
+                S = np.concatenate([rsum(f(xs)), rsum(f(out[m]) * f(li["out_my"][m])), rsum(f(out[m]))], -1).reshape(B * T, 3)
+                xs_all[m] = xs
+                if mutant == "out_S_rows_by_t":
+                    for row in range(B * T):
+                        S_all[m, row % T] = S[row]
+                else:
+                    S_all[m] = S
+            got.update(xs=xs_all, S=S_all)
+    return got if full else (out, cur)
+
+
+# Defects of a launch form that the reference must reject (tests/test_tmix_ref_cpu.py), each the counterpart of one line of the kernel
+LN_MUTANTS = ["group_shift_from_carry", "carry_from_last_full_group", "planes_summed_in_binary16", "planes_beyond_PL_dropped",
+              "delta_added_unrounded", "offset_1024", "S_parts_beyond_64_dropped", "S1_S2_swapped", "prologue_ry_of_plane_0",
+              "out_S_rows_by_t"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
