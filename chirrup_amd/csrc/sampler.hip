@@ -288,6 +288,14 @@ extern "C" int rwkv7_commit_sampled_listed(int n, int V, const int32_t *ids, con
 // order with a caller-supplied uniform number per row (torch's generator stays the source of
 // randomness).  Differences from the reference: ties AT the top-k boundary are all kept, and the
 // draw uses one uniform instead of torch.multinomial's stream -- same distribution, different ids.
+// The draw: lane t owns the ids [t per, (t + 1) per), per = ceil(V / 1024), and adds its kept weights
+// (local); an inclusive scan over each wave and the 16 wave sums in order give before_t, the CDF in
+// front of the lane, and the total; want = u * total.  The highest lane with local > 0 and before <=
+// want walks its chunk: the first token of positive weight whose running sum exceeds want, its last
+// token of positive weight when none does (two lanes' bounds of one point of the CDF come from
+// different trees of binary32 additions and may leave an ulp between them).  Only when no lane has
+// weight does lane 0 fall back to the last kept token.  tests/sampler_ref.py holds the binary64
+// admissible-set reference of all this, tests/test_sample_topp_ref_gpu.py the cases.
 namespace {
 
 constexpr int kSampThreads = 1024;
@@ -540,6 +548,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_topp_kernel(
         const float t = __shfl_up(incl, o, 64);
         if ((tid & 63) >= o) incl += t;
     }
+    int *claim = reinterpret_cast<int *>(scal + 4);      // [0] the lane that draws, [1] its pick
+    if (tid == 0) claim[0] = -1, claim[1] = -1;
     __syncthreads();
     if ((tid & 63) == 63) red[tid >> 6] = incl;
     __syncthreads();
@@ -547,12 +557,20 @@ __global__ __launch_bounds__(kSampThreads) void sample_topp_kernel(
     for (int i = 0; i < kSampThreads / 64; i++) { if (i < (tid >> 6)) wave_base += red[i]; total += red[i]; }
     const float before = wave_base + incl - local;
     const float want = uniform[blockIdx.x] * total;
-    if (tid == 0) scal[4] = -1.f;
+    // Lane t's interval of the CDF starts at before_t, and before_{t+1} reaches the point where it ends through another tree of
+    // binary32 additions: the two can differ by an ulp either way, and before can even step back by an ulp past a tiny local.  So
+    // a lane does not test the END of its interval (a `want` in a one-ulp gap between two lanes would belong to nobody): the
+    // HIGHEST lane of positive weight whose interval starts at or below `want` draws.  Every want >= 0 has such a lane unless
+    // every weight underflowed (the first lane of positive weight has before = 0), and its chunk is adjacent to want in the CDF.
+    // (a lane whose upper neighbour in the wave also qualifies leaves the LDS atomic to it: same-address atomics serialise)
+    const int mine = local > 0.f && before <= want;
+    const int upper = __shfl_down(mine, 1, 64);
+    if (mine && ((tid & 63) == 63 || !upper)) atomicMax(claim, tid);
     __syncthreads();
     // only tokens of positive weight can be drawn: a kept token whose weight is 0 (a forbidden -inf logit kept by top_p = 1, a
-    // p^(1/T) that underflows) is stepped over -- else the walk, when its running sum never exceeds `want` by rounding, or the
-    // fall-back below would return it
-    if (local > 0.f && want >= before && want < before + local) {
+    // p^(1/T) that underflows) is stepped over.  When the running sum never exceeds `want` (want in a rounding gap behind this
+    // lane's interval, or at or beyond the last lane's bound, u -> 1) the lane's last token of positive weight is the draw.
+    if (tid == claim[0]) {
         float acc = before; int pick = -1;
         for (int c = c0; c < c1; c++) {
             if (key_of(row[c]) >= thr) {
@@ -564,13 +582,13 @@ __global__ __launch_bounds__(kSampThreads) void sample_topp_kernel(
                 }
             }
         }
-        scal[4] = (float)pick;           // one thread's interval contains `want` (two may, by rounding: either pick is valid)
+        claim[1] = pick;
     }
     __syncthreads();
     if (tid == 0) {
-        int pick = (int)scal[4];
-        if (pick < 0) {                  // no interval holds `want` (u -> 1, or a rounding gap between two lanes' intervals): the
-                                         // last kept token of positive weight; the last kept token if every weight underflowed
+        int pick = claim[1];
+        if (pick < 0) {                  // no lane has positive weight (every weight underflowed; or u is not a number): the last
+                                         // kept token of positive weight if there is one, else the last kept token
             int last = -1;
             for (int c = V - 1; c >= 0; c--) {
                 if (key_of(row[c]) >= thr) {
