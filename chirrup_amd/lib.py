@@ -105,6 +105,13 @@ SIGNATURES = {
     "mm8t_exact_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "mm8t_seq_exact": (_i, [_i, _i, _i, _vp, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "skinny_tile_weight_u8": (_i, [_i, _i, _vp, _i64, _vp, _vp]),
+    "mxfp4_tiled_bytes": (_i64, [_i, _i]),
+    "mxfp4_tile_weight": (_i, [_i, _i, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mxfp4_dequant_f16": (_i, [_i, _i, _vp, _vp, _i64, _vp]),
+    "mxfp4_gemm_splits": (_i, [_i, _i, _i, _i]),
+    "mxfp4_gemm_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "mxfp4_gemm": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mxfp4_gemm_partial": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _f32p, _vp]),
 }
 
 

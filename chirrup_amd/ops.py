@@ -1027,6 +1027,109 @@ def mm8_dequant(wT, mx, rx, my, ry, tiled: bool = False, out=None) -> torch.Tens
     return out.view(-1)[: M * N].view(M, N)
 
 
+class TiledMxfp4:
+    """An MXFP4 weight [M_out, N_in] as the tile images of csrc/mxfp4.hip (include/chirrup_amd.h: mxfp4_tile_weight): `data` is the
+    flat uint8 tensor, 4.25 bits per weight.  quant.untile_mxfp4 gives the row-major codes and scales back."""
+    __slots__ = ("data", "shape")
+
+    def __init__(self, data: torch.Tensor, m_out: int, n_in: int):
+        self.data, self.shape = data, (m_out, n_in)
+
+
+def tile_weight_mxfp4(w) -> TiledMxfp4:
+    """quant.Mxfp4Weight (GPU tensors; M_out % 128 == 0, N_in % 64 == 0, scale bytes within 2^-13 .. 2^13 -- anything else is refused
+    here, on the host) -> a NEW TiledMxfp4."""
+    from .quant import check_mxfp4
+
+    check_mxfp4(w)
+    codes, scales = w.codes, w.scales
+    if not codes.is_cuda or not scales.is_cuda or codes.stride(1) != 1 or scales.stride(1) != 1:
+        raise _lib.ChirrupAmdError("tile_weight_mxfp4: expected GPU uint8 codes and scales with unit inner stride")
+    M, N = codes.shape[0], codes.shape[1] * 2
+    L = _lib.load()
+    nbytes = L.mxfp4_tiled_bytes(M, N)
+    if nbytes == 0:
+        raise _lib.ChirrupAmdError(f"tile_weight_mxfp4: [{M}, {N}] needs M_out % 128 == 0 and N_in % 64 == 0")
+    out = torch.empty((nbytes,), dtype=torch.uint8, device=codes.device)
+    rc = L.mxfp4_tile_weight(M, N, codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), out.data_ptr(), _stream())
+    _lib.check(rc, "mxfp4_tile_weight")
+    return TiledMxfp4(out, M, N)
+
+
+def _chk_mxfp4(W, K: Optional[int] = None):
+    if not isinstance(W, TiledMxfp4) or not W.data.is_cuda or W.data.dtype != torch.uint8 or not W.data.is_contiguous():
+        raise _lib.ChirrupAmdError("W: expected a TiledMxfp4 (ops.tile_weight_mxfp4)")
+    if K is not None and W.shape[1] != K:
+        raise _lib.ChirrupAmdError("W: K mismatch")
+    return W.shape
+
+
+def mxfp4_dequant(W: TiledMxfp4, out=None) -> torch.Tensor:
+    """The dequantised matrix w~ as binary16 [M_out, N_in], exact (include/chirrup_amd.h: mxfp4_dequant_f16): what a forward of more
+    than 256 rows multiplies through the library GEMM.  out: a [M_out, N_in] fp16 matrix with unit inner stride (may be a row-strided
+    view), or a contiguous scratch of at least M_out * N_in elements."""
+    M, N = _chk_mxfp4(W)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=W.data.device)
+    if not out.is_cuda or out.dtype != torch.float16:
+        raise _lib.ChirrupAmdError("out: expected a GPU fp16 tensor")
+    if out.dim() == 2 and tuple(out.shape) == (M, N) and out.stride(1) == 1:
+        view = out
+    elif out.is_contiguous() and out.numel() >= M * N:
+        view = out.view(-1)[: M * N].view(M, N)
+    else:
+        raise _lib.ChirrupAmdError("out: expected [M_out, N_in] with unit inner stride or a contiguous buffer of M_out * N_in elements")
+    rc = _lib.load().mxfp4_dequant_f16(M, N, W.data.data_ptr(), view.data_ptr(), view.stride(0), _stream())
+    _lib.check(rc, "mxfp4_dequant_f16")
+    return view
+
+
+def mxfp4_linear(x, W: TiledMxfp4, act: int = 0, splits: int = 0, out=None):
+    """y = act(x @ w~.T): x [M <= 256, K] fp16 against MXFP4 weights through csrc/mxfp4.hip -- exact products, binary32 accumulation, one
+    rounding to binary16 after act (1 = relu(.)**2).  splits: K-slices (0 = the library's choice)."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float16 or x.stride(1) != 1:
+        raise _lib.ChirrupAmdError("mxfp4_linear: expected x [M,K] GPU fp16 with unit inner stride")
+    M, K = x.shape
+    N, _ = _chk_mxfp4(W, K)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    elif not out.is_cuda or out.dtype != torch.float16 or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise _lib.ChirrupAmdError("mxfp4_linear: out must be GPU fp16 [M, N] with unit inner stride")
+    L = _lib.load()
+    nbytes = L.mxfp4_gemm_workspace_bytes(M, N, K, splits)
+    ws = _workspace(nbytes + 256, x.device) if nbytes else None
+    base = (ws.data_ptr() + 255) // 256 * 256 if ws is not None else None
+    rc = L.mxfp4_gemm(M, N, K, x.data_ptr(), x.stride(0), W.data.data_ptr(), out.data_ptr(), out.stride(0), act, splits, base, _stream())
+    _lib.check(rc, "mxfp4_gemm")
+    return out
+
+
+def mxfp4_gemm_splits(M: int, N: int, K: int, splits: int = 0) -> int:
+    """The K-slice count mxfp4_linear / mxfp4_linear_partial use for these arguments (sizing partial buffers)."""
+    return _lib.load().mxfp4_gemm_splits(M, N, K, splits)
+
+
+def mxfp4_linear_partial(x, W: TiledMxfp4, splits: int, partials):
+    """Split-K partial sums of x @ w~.T into `partials` (fp32, room for [splits_used, M, N]); returns that view.  The consumer
+    (add_ln_mix(delta_partials=...)) adds the planes."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float16 or x.stride(1) != 1:
+        raise _lib.ChirrupAmdError("mxfp4_linear_partial: expected x [M,K] GPU fp16 with unit inner stride")
+    M, K = x.shape
+    N, _ = _chk_mxfp4(W, K)
+    if not partials.is_cuda or partials.dtype != torch.float32 or not partials.is_contiguous():
+        raise _lib.ChirrupAmdError("partials: expected contiguous GPU fp32")
+    L = _lib.load()
+    s = L.mxfp4_gemm_splits(M, N, K, splits)
+    if s <= 0:
+        raise _lib.ChirrupAmdError(f"mxfp4_linear_partial: shape [{M}, {K}] x [{N}, {K}] refused")
+    if partials.numel() < s * M * N:
+        raise _lib.ChirrupAmdError("partials buffer too small")
+    rc = L.mxfp4_gemm_partial(M, N, K, x.data_ptr(), x.stride(0), W.data.data_ptr(), splits, partials.data_ptr(), _stream())
+    if rc <= 0:
+        raise _lib.ChirrupAmdError(f"mxfp4_gemm_partial: {rc}")
+    return partials.view(-1)[: rc * M * N].view(rc, M, N)
+
+
 def mm8t_gemm_partial(xs, wT, M_out: int, splits: int, partials, tiled: bool = False, row_halves: bool = False):
     """The matrix product of mm8t_linear alone: xs [B<=256, N_in] fp16 (an mm8 prologue's output) against wT; fp32 core sums
     into `partials`, returned as the view [splits_used, B, M_out] (include/chirrup_amd.h: mm8t_gemm_partial)."""

@@ -1,4 +1,4 @@
-"""mm8 (w8a16) weight quantisation, host side.
+"""Weight quantisation, host side: mm8 (w8a16, below) and MXFP4 (w4a16, second half of the file).
 
 Restates the reference's quantize_weight (scripts/test_mm8/benchmark.py:54-85, the rwkv pip package's
 scheme): for w [N_in, M_out] subtract column minima mx and row minima my (order depends on the
@@ -52,3 +52,89 @@ def untile_u8(flat: torch.Tensor, m_out: int, n_in: int) -> torch.Tensor:
     rows = torch.gather(img, 3, pos.view(1, 1, 128, 4, 1).expand(m_out // 128, n_in // 64, 128, 4, 16))
     return rows.permute(0, 2, 1, 3, 4).reshape(m_out, n_in).contiguous()
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MXFP4 (w4a16): OCP Microscaling FP4, blocks of 32 along K (include/chirrup_amd.h: mxfp4_*)
+
+MXFP4_BLOCK = 32
+MXFP4_E_MIN, MXFP4_E_MAX = -13, 13               # 0.5 * 2^e is a normal binary16 number and 6 * 2^e is finite
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_TILE_BYTES = 128 * 32 + 128 * 2            # one (128 rows x 64 k) tile image: codes, then scales
+
+
+class Mxfp4Weight(NamedTuple):
+    codes: torch.Tensor    # uint8 [M_out, N_in / 2]: byte j of a row holds k = 2 j (low nibble) and 2 j + 1 (high nibble); bit 3 = sign
+    scales: torch.Tensor   # uint8 [M_out, N_in / 32]: E8M0, the block's weights are E2M1(code) * 2^(scale - 127)
+
+
+def check_mxfp4(w: Mxfp4Weight) -> None:
+    """Refuse what the kernels do not define: mismatched shapes, scale bytes outside 2^-13 .. 2^13 (0xFF, the format's NaN, too)."""
+    c, s = w.codes, w.scales
+    if c.dtype != torch.uint8 or s.dtype != torch.uint8 or c.dim() != 2 or s.dim() != 2:
+        raise ValueError("Mxfp4Weight: codes and scales must be uint8 matrices")
+    if c.shape[0] != s.shape[0] or c.shape[1] * 2 != s.shape[1] * MXFP4_BLOCK or c.shape[1] == 0:
+        raise ValueError(f"Mxfp4Weight: codes {tuple(c.shape)} and scales {tuple(s.shape)} do not describe one [M_out, N_in] matrix")
+    if s.numel():
+        lo, hi = int(s.min()), int(s.max())
+        if lo < 127 + MXFP4_E_MIN or hi > 127 + MXFP4_E_MAX:
+            raise ValueError(f"Mxfp4Weight: scale bytes {lo}..{hi} outside {127 + MXFP4_E_MIN}..{127 + MXFP4_E_MAX} "
+                             f"(block exponents {MXFP4_E_MIN}..{MXFP4_E_MAX})")
+
+
+def quantize_linear_mxfp4(weight: torch.Tensor) -> Mxfp4Weight:
+    """A Linear weight [M_out, N_in] (y = x @ W.T) -> MXFP4: per 32-block along N_in the exponent e = clamp(ceil(log2(amax / 6)),
+    -13, 13), i.e. the SMALLEST scale at which the block's largest element does not saturate (6 * 2^(e-1) < amax <= 6 * 2^e; the OCP
+    specification's rule is floor(log2(amax)) - 2, which lets elements above 6 * 2^e clamp -- here |w - w~| <= 2^e for every element
+    of an unclamped block); an all-zero block takes e = -13.  Elements: nearest value of the E2M1 grid, ties to the even code,
+    clamped to +-6 (which only a block clamped at e = 13 can need).  Deterministic: no random rounding, exact comparisons in binary64."""
+    if weight.dim() != 2 or weight.shape[1] % MXFP4_BLOCK or weight.shape[1] == 0 or weight.shape[0] == 0 or not weight.dtype.is_floating_point:
+        raise ValueError(f"quantize_linear_mxfp4: expected a floating-point [M_out, N_in] matrix with N_in % {MXFP4_BLOCK} == 0, "
+                         f"got {tuple(weight.shape)} {weight.dtype}")
+    M, N = weight.shape
+    w = weight.detach().to(torch.float64).reshape(M, N // MXFP4_BLOCK, MXFP4_BLOCK)
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_linear_mxfp4: the weight holds NaN or inf")
+    amax = w.abs().amax(-1)
+    _, ex = torch.frexp(amax / 6.0)                                  # amax / 6 = m 2^ex, m in [0.5, 1): ceil(log2) is ex or ex - 1
+    e = ex.to(torch.int64)
+    e = torch.where(torch.ldexp(torch.full_like(amax, 6.0), e - 1) >= amax, e - 1, e)      # exact: amax <= 6 * 2^(e-1)
+    e = torch.where(torch.ldexp(torch.full_like(amax, 6.0), e) < amax, e + 1, e)
+    e = torch.where(amax == 0, torch.full_like(e, MXFP4_E_MIN), e).clamp(MXFP4_E_MIN, MXFP4_E_MAX)
+    y = torch.ldexp(w.abs(), (-e).unsqueeze(-1).expand_as(w)).clamp(max=6.0)                # exact scaling by a power of two
+    # grid midpoints; a tie goes to the even code: 0.25 -> 0, 0.75 -> 2, 1.25 -> 2, 1.75 -> 4, 2.5 -> 4, 3.5 -> 6, 5 -> 6
+    code = ((y > 0.25).to(torch.uint8) + (y >= 0.75).to(torch.uint8) + (y > 1.25).to(torch.uint8) + (y >= 1.75).to(torch.uint8)
+            + (y > 2.5).to(torch.uint8) + (y >= 3.5).to(torch.uint8) + (y > 5.0).to(torch.uint8))
+    code = code | (((w < 0) & (code > 0)).to(torch.uint8) << 3)      # (no negative zeros)
+    code = code.reshape(M, N // 2, 2)
+    codes = (code[..., 0] | (code[..., 1] << 4)).contiguous()
+    return Mxfp4Weight(codes, (e + 127).to(torch.uint8).contiguous())
+
+
+def dequantize_mxfp4(w: Mxfp4Weight) -> torch.Tensor:
+    """w~ as binary16 [M_out, N_in], exact: E2M1(code) * 2^(scale - 127)."""
+    check_mxfp4(w)
+    c = w.codes
+    M, N = c.shape[0], c.shape[1] * 2
+    nib = torch.stack([c & 15, c >> 4], -1).reshape(M, N).long()
+    table = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=c.device)
+    e = (w.scales.to(torch.int32) - 127).repeat_interleave(MXFP4_BLOCK, dim=1)
+    v = torch.ldexp(table[nib], e)
+    out = v.to(torch.float16)
+    assert bool((out.float() == v).all())
+    return out
+
+
+def mxfp4_tiled_bytes(m_out: int, n_in: int) -> int:
+    return (m_out // 128) * (n_in // 64) * MXFP4_TILE_BYTES
+
+
+def untile_mxfp4(flat: torch.Tensor, m_out: int, n_in: int) -> Mxfp4Weight:
+    """Inverse of ops.tile_weight_mxfp4 (inspection / tests): flat tile images -> the row-major Mxfp4Weight.  Tile (g, b) is 4352 bytes:
+    128 rows x 32 code bytes, position 8 q + 4 s + j of a row holding logical byte 16 s + 4 q + j of the K-block (k = 32 s + 8 q + 2 j, + 1),
+    then 128 rows x 2 scale bytes."""
+    G, B = m_out // 128, n_in // 64
+    img = flat.view(G, B, MXFP4_TILE_BYTES)
+    codes = img[..., :4096].reshape(G, B, 128, 4, 2, 4).permute(0, 2, 1, 4, 3, 5).reshape(m_out, n_in // 2)     # [g, r, b, s, q, j]
+    scales = img[..., 4096:].reshape(G, B, 128, 2).permute(0, 2, 1, 3).reshape(m_out, n_in // 32)
+    return Mxfp4Weight(codes.contiguous(), scales.contiguous())

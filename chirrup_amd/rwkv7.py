@@ -85,7 +85,7 @@ class _Layer:
     __slots__ = ("ln1_w", "ln1_b", "ln2_w", "ln2_b", "x_r", "x_w", "x_k", "x_v", "x_a", "x_g", "w0", "w1", "w2", "a0", "a1",
                  "a2", "v0", "v1", "v2", "g1", "g2", "k_k", "k_a", "r_k", "R", "K", "V", "O", "lnx_w", "lnx_b", "f_x_k",
                  "f_K", "f_V", "mix6", "rkv", "lora1", "lora2", "lora_k", "lbias", "f_K8", "f_V8", "f_V_rows",
-                 "rkv_t", "O_t", "f_K_t", "f_V_t", "lora2_t", "f8_tiled", "R8", "K8", "V8", "O8", "a8_tiled", "rkv8_ry", "rkv8_my")
+                 "rkv_t", "O_t", "f_K_t", "f_V_t", "lora2_t", "f8_tiled", "f_K4", "f_V4", "R8", "K8", "V8", "O8", "a8_tiled", "rkv8_ry", "rkv8_my")
 
     def __init__(self, z, i):
         b, a, f = f"blocks.{i}.", f"blocks.{i}.att.", f"blocks.{i}.ffn."
@@ -170,6 +170,19 @@ class _Layer:
         del z[f + "key.weight"], z[f + "value.weight"]
         self.f_K = self.f_V = None
 
+    def quantize_ffn_mxfp4(self, z, i):
+        """MXFP4 (w4a16) channel-mix: quantise ffn.key / ffn.value (quant.quantize_linear_mxfp4: blocks of 32 along the reduction
+        dimension) and keep ONLY their tile images (csrc/mxfp4.hip); the fp16 copies are dropped.  z keeps '<key>.mxfp4' ->
+        ops.TiledMxfp4 instead of the fp16 tensor.  Shapes the tile images cannot hold (C % 128) are refused here, at load."""
+        from .quant import quantize_linear_mxfp4
+
+        f = f"blocks.{i}.ffn."
+        self.f_K4 = ops.tile_weight_mxfp4(quantize_linear_mxfp4(self.f_K))          # Linear weight [4C, C]
+        self.f_V4 = ops.tile_weight_mxfp4(quantize_linear_mxfp4(self.f_V.t()))      # f_V is the [4C, C] view of the [C, 4C] Linear weight
+        z[f + "key.weight.mxfp4"], z[f + "value.weight.mxfp4"] = self.f_K4, self.f_V4
+        del z[f + "key.weight"], z[f + "value.weight"]
+        self.f_K = self.f_V = None
+
 
 def _quantize_att(lw, z, i, tile: bool = False):
     """mm8 (w8a16) time-mix projections: receptance / key / value / output quantised like the reference's quantize_weight
@@ -233,8 +246,10 @@ class _Plan(NamedTuple):
     lora: str                   # LoRA chain: launch (in the R/K/V launch) | grouped | per_problem | bmm_ring | bmm_baddbmm
     side: bool                  # the LoRA chain on the side stream, beside R/K/V on this one
     att_out: str                # att.output: mm8_fused (prologue from the core) | mm8 | ring (partials into LN2) | library
-    ffn_key: str                # mm8_fused | mm8_pair | mm8_partial (+ reduce) | mm8_dequant | mm8 | ring (+ relu^2) | mm_nt
-    ffn_value: str              # mm8_parts (into the next LN) | mm8_dequant | mm8 | sparse | ring (partials) | mm_nt | matmul
+    ffn_key: str                # mm8_fused | mm8_pair | mm8_partial (+ reduce) | mm8_dequant | mm8 | ring (+ relu^2) | mm_nt |
+                                # mxfp4 (relu^2 in the epilogue) | mxfp4_dequant
+    ffn_value: str              # mm8_parts (into the next LN) | mm8_dequant | mm8 | sparse | ring (partials) | mm_nt | matmul |
+                                # mxfp4_parts (binary32 planes into the next LN) | mxfp4_dequant
     head: str                   # mm8 | ring | library
 
 
@@ -243,7 +258,7 @@ def plan_forward(knobs, rows: int, T: int, C: int, layer) -> _Plan:
     attributes; `layer`: anything with _Layer's tiling facts (a8_tiled, f8_tiled, rkv_t, lora2_t, f_V_rows).  Host only."""
     gs, a8, f8 = knobs.gemm_splits, knobs.att_dtype == torch.int8, knobs.ffn_dtype == torch.int8
     hw = knobs.skinny_ffn_value and knobs.skinny_min_rows <= rows <= 256 and C >= knobs.skinny_min_embd
-    use_parts = hw and not f8
+    use_parts = hw and not f8 and knobs.ffn_dtype != "mxfp4"
     # chunks of many tokens: gating, decay and group norm in row-parallel launches around a recurrence-only scan
     fuse_core = knobs.fuse_tmix_core and not (knobs.split_tmix_min_T and T >= knobs.split_tmix_min_T)
     rh = knobs.gemm_row_halves if rows >= knobs.row_halves_min_rows else dict.fromkeys(knobs.gemm_row_halves, False)
@@ -257,7 +272,10 @@ def plan_forward(knobs, rows: int, T: int, C: int, layer) -> _Plan:
             "bmm_ring" if knobs.skinny_lora_up else "bmm_baddbmm")
     att_out = (("mm8_fused" if hw and T == 1 and fuse_core and knobs.skinny_att_out else "mm8") if a8 else
                "ring" if hw and knobs.skinny_att_out and rows >= knobs.skinny_wide_rows else "library")
-    if f8 and hw and T == 1:
+    if knobs.ffn_dtype == "mxfp4":
+        # up to 256 rows the MXFP4 GEMM (csrc/mxfp4.hip), above: the dequantised matrix through the library GEMM -- the same matrix
+        ffn_key, ffn_value = ("mxfp4", "mxfp4_parts") if rows <= 256 else ("mxfp4_dequant", "mxfp4_dequant")
+    elif f8 and hw and T == 1:
         # ffn.key's corrections + relu^2 + ffn.value's prologue in the key GEMM's epilogue (unsplit launch, row halves); few rows:
         # the key product split over K and reduced by each tile's last workgroup, with the same epilogue -- no reduce launch
         ffn_key, ffn_value = "mm8_partial", "mm8_parts"
@@ -373,15 +391,20 @@ class RWKV_x070:
         # RWKV_x070_CMix_one + rwkv_mm_sparsity, rwkv7.py:653-662); needs the [4C, C] row layout, so it
         # keeps one extra copy of ffn.value per layer -- meant for the small single-stream configs
         self.sparse_bsz1 = bool(sparse_bsz1) and fused and self.device.type == "cuda" and ffn_dtype == torch.float16
-        if ffn_dtype not in (torch.float16, torch.int8):
-            raise ValueError("ffn_dtype must be torch.float16 or torch.int8 (mm8, w8a16)")
+        if ffn_dtype not in (torch.float16, torch.int8, "mxfp4"):
+            raise ValueError('ffn_dtype must be torch.float16, torch.int8 (mm8, w8a16) or "mxfp4" (w4a16)')
         if ffn_dtype == torch.int8 and not self.fused:
             raise ops._lib.ChirrupAmdError("the mm8 channel-mix path needs the HIP kernels (a GPU, fused=True)")
+        if ffn_dtype == "mxfp4" and not self.fused:
+            raise ops._lib.ChirrupAmdError("the MXFP4 channel-mix path needs the HIP kernels (a GPU, fused=True)")
         if self.fused:
             for i, lw in enumerate(self._layers):
                 lw.pack_for_fused(self.z, i)
                 if ffn_dtype == torch.int8:
                     lw.quantize_ffn(self.z, i, tile=self.tiled_weights)
+                lw.f_K4 = lw.f_V4 = None
+                if ffn_dtype == "mxfp4":
+                    lw.quantize_ffn_mxfp4(self.z, i)
                 lw.f_V_rows = lw.f_V.contiguous() if self.sparse_bsz1 else None
                 lw.rkv_t = lw.O_t = lw.f_K_t = lw.f_V_t = lw.lora2_t = None
                 lw.R8 = lw.K8 = lw.V8 = lw.O8 = lw.rkv8_ry = lw.rkv8_my = None
@@ -523,7 +546,7 @@ class RWKV_x070:
                 if isinstance(z, _LazyWeights) and k in z._lazy:
                     tot += z.nbytes_of(k)                    # lives as a tile image of the same size
                     continue
-                t = z[k] if k in z else z[k + ".mm8"]
+                t = z[k] if k in z else z[k + ".mm8"] if k + ".mm8" in z else z[k + ".mxfp4"].data
                 tot += sum(x.numel() * x.element_size() for x in (t if isinstance(t, tuple) else (t,)))
             return tot
 
@@ -730,6 +753,8 @@ class RWKV_x070:
         # split-K partials of att.output (or the uint8 att.output's core partials) and of ffn.value, summed by the next LN kernel
         f.pbuf_o = f32(ops.gemm_splits(C, C, 1, gs["att_out"]), rows, C) if p.att_out in ("ring", "mm8_fused") else None
         f.pbuf = f32(ops.gemm_splits(C, 4 * C, 1, gs["ffn_value"]), rows, C) if p.use_parts or p.ffn_value == "mm8_parts" else None
+        if p.ffn_value == "mxfp4_parts":
+            f.pbuf = f32(ops.mxfp4_gemm_splits(rows, C, 4 * C, gs["ffn_value"]), rows, C)
         f.S_o = f32(rows, self.n_head, 3) if p.att_out == "mm8_fused" else None
         f.xs_rkv, f.S_rkv = (new(3, rows, C), f32(3, rows, 3)) if p.rkv == "chain_mm8" else (None, None)
         if p.ffn_value == "mm8_parts":
@@ -889,6 +914,22 @@ class RWKV_x070:
         elif p.ffn_value == "mm8":                  # mm8 on the matrix cores, relu^2 fused into the epilogue
             kf = ops.mm8t_linear(kin, *lw.f_K8, act=1, tiled=lw.f8_tiled)
             f.delta = ops.mm8t_linear(kf, *lw.f_V8, tiled=lw.f8_tiled).view(B, T, C)
+        elif p.ffn_value == "mxfp4_parts":
+            # MXFP4 weights dequantised in registers in front of the MFMAs; ffn.value's K-slices are plain binary32 sums of the
+            # product with the dequantised matrix, so the next LN kernel adds them like the binary16 ring GEMM's planes
+            kf = ops.mxfp4_linear(kin, lw.f_K4, act=1, splits=gs["ffn_key"])
+            f.dparts = ops.mxfp4_linear_partial(kf, lw.f_V4, gs["ffn_value"], f.pbuf)
+        elif p.ffn_value == "mxfp4_dequant":
+            # chunked prefill: the dequantised matrices (exact) into the scratch pair of the uint8 path, then the library GEMM --
+            # decode and prefill multiply by the same matrix
+            sK, sV = self._mm8_scratch(4 * C * C)
+            wK16 = ops.mxfp4_dequant(lw.f_K4, out=sK)                            # [4C, C]
+            kf = f.new(B, T, 4 * C)
+            self._mm_nt(kin, wK16, kf.view(rows, 4 * C))
+            ops.relu_sq_(kf)
+            wV16 = ops.mxfp4_dequant(lw.f_V4, out=sV)                            # [C, 4C]
+            f.delta = f.new(B, T, C)
+            self._mm_nt(kf.view(rows, 4 * C), wV16, f.delta.view(rows, C))
         else:
             if p.ffn_key == "ring":
                 kf = ops.skinny_linear(kin, lw.ring("f_K"), act=1, splits=gs["ffn_key"], row_halves=rh["ffn_key"])

@@ -314,7 +314,8 @@ class Worker:
         if self.model is None:
             self.model = RWKV_x070(model_args(self.model_config.model_path, self.model_config.vocab_size,
                                               self.model_config.head_size),
-                                   ffn_dtype=torch.int8 if self.model_config.dtype == torch.int8 else torch.float16,
+                                   ffn_dtype=(torch.int8 if self.model_config.dtype == torch.int8 else
+                                              "mxfp4" if self.model_config.dtype == "mxfp4" else torch.float16),
                                    att_dtype=torch.int8 if getattr(self.model_config, "att_dtype", None) == torch.int8 else torch.float16)
         if self.tokenizer is None:
             self.tokenizer = TRIE_TOKENIZER(self.model_config.vocab_path)

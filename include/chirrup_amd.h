@@ -697,6 +697,35 @@ int mm8t_gemm_fused_split(int B, int N_in, int M_out, const void *xs, int xs_str
                           const void *ry2, const void *my2, void *xs2, float *S2, int splits, float *partials,
                           void *tile_counters, void *stream);
 
+/*
+ * MXFP4 (w4a16) weights, csrc/mxfp4.hip: OCP Microscaling FP4.  A block of 32 E2M1 codes along K (the reduction dimension, N_in of
+ * the Linear) shares one E8M0 scale byte s:  w~[n][k] = E2M1(code[n][k]) * 2^(s[n][k / 32] - 127);  code bit 3 is the sign, codes
+ * 0..7 are 0, .5, 1, 1.5, 2, 3, 4, 6.  The caller passes only scale bytes 114..140 (2^-13 .. 2^13: every w~ is then +-0 or a normal
+ * binary16 number); the kernels do not define anything else (chirrup_amd.quant refuses it on the host).
+ *
+ * mxfp4_tile_weight: codes [M_out][N_in / 2] uint8 row-major (row stride ld_codes bytes, a multiple of 4; low nibble = even k) and
+ *   scales [M_out][N_in / 32] uint8 (row stride ld_scales) -> Wt, mxfp4_tiled_bytes(M_out, N_in) bytes (0: shape refused) of tile
+ *   images: tile (n / 128, k / 64) is 4352 consecutive bytes, 128 rows x 32 code bytes then 128 rows x 2 scale bytes; code byte
+ *   position 8 q + 4 s + j of a row holds k = 32 s + 8 q + 2 j, + 1 of the K-block.  M_out % 128 == 0, N_in % 64 == 0.
+ * mxfp4_dequant_f16: Wt -> w~ as binary16 [M_out][N_in], row stride ld_out elements (a multiple of 8), exact.  What a forward of
+ *   more than 256 rows multiplies through the library GEMM, like mm8_dequant_f16.
+ * mxfp4_gemm: Y [M][N] = act(X [M][K] . w~ [N][K]^T), M = 1..256 rows, N % 128 == 0, K % 64 == 0: exact products, binary32
+ *   accumulation, ONE rounding to binary16 after act (0 none, 1 relu(fp16(.))^2).  splits: K-slices (0 = the library's choice; cut
+ *   back to a divisor of K / 64: mxfp4_gemm_splits tells); workspace: mxfp4_gemm_workspace_bytes, 16-byte aligned, needed above one
+ *   slice.  X 16-byte aligned, ldx % 8 == 0; Y 8-byte aligned, ldy % 4 == 0.
+ * mxfp4_gemm_partial: the K-slices' binary32 sums as planes partials [splits_used][M][N] (16-byte aligned) for a consumer that
+ *   adds them (rwkv7_add_ln_mix: delta_partials).  Returns splits_used, or -1000 - error.
+ */
+int64_t mxfp4_tiled_bytes(int M_out, int N_in);
+int mxfp4_tile_weight(int M_out, int N_in, const void *codes, int64_t ld_codes, const void *scales, int64_t ld_scales, void *Wt,
+                      void *stream);
+int mxfp4_dequant_f16(int M_out, int N_in, const void *Wt, void *out, int64_t ld_out, void *stream);
+int mxfp4_gemm_splits(int M, int N, int K, int splits);
+int64_t mxfp4_gemm_workspace_bytes(int M, int N, int K, int splits);
+int mxfp4_gemm(int M, int N, int K, const void *X, int ldx, const void *Wt, void *Y, int ldy, int act, int splits, void *workspace,
+               void *stream);
+int mxfp4_gemm_partial(int M, int N, int K, const void *X, int ldx, const void *Wt, int splits, float *partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
