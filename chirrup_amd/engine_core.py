@@ -104,14 +104,18 @@ class AsyncEngineCore:
 
     def __init__(self, worker_factory: Optional[Callable[..., Any]] = None, tokenizer=None, worker_mode: str = "thread",
                  worker_kwargs: Optional[Dict[str, Any]] = None, state_arena_rows: int = 0, prefix_affinity: bool = True,
-                 gpu_ids: Optional[List[int]] = None):
+                 gpu_ids: Optional[List[int]] = None, state_arena_format: Optional[str] = None):
         """worker_factory(**worker_args) -> object with .start(): defaults to chirrup_amd.worker.Worker; in process mode it is
         called INSIDE the worker process and must be picklable (a module-level function).  worker_kwargs: extra Worker
         arguments (e.g. run_ahead).  state_arena_rows (process mode): rows of the HBM prefix-state arena EVERY worker process
         builds on its GPU; ``self.state_arena`` is then the engine-side view to hand to ``SimpleStateCache(arena=...)`` -- prefix
         states never leave HBM (chirrup_amd/remote_arena.py).  prefix_affinity=False queues hits on the shared queue instead of
         the owning worker's, "avoid" on ANOTHER worker's (tests: every hit is then installed through the owner's IPC handle).  gpu_ids: device of
-        worker k (default k)."""
+        worker k (default k).  state_arena_format="mxint8": those arenas keep the head states packed (HbmStateArena(wkv_format=):
+        about half the bytes per row; a hit continues from the codec's round trip of the exported state)."""
+        if state_arena_format not in (None, "mxint8"):
+            raise ValueError("state_arena_format must be None or 'mxint8'")
+        self.state_arena_format = state_arena_format
         if worker_mode not in ("thread", "process", "auto"):
             raise ValueError("worker_mode must be 'thread', 'process' or 'auto'")
         self.worker_mode = worker_mode
@@ -158,6 +162,8 @@ class AsyncEngineCore:
             from .remote_arena import RemoteArena
 
             kwargs["state_arena_rows"] = self.state_arena_rows
+            if self.state_arena_format is not None:
+                kwargs["state_arena_format"] = self.state_arena_format
             kwargs["arena_steal"] = self.prefix_affinity != "avoid"      # ("avoid": tests -- the owner must not take its hits back)
             self.state_arena = RemoteArena(self.state_arena_rows, worker_num, self._send_arena_free)
         self._router = ep.ResultRouter(self._result_q, self.worker_event_queue, self._on_process_worker_exit, self.state_arena)
@@ -165,7 +171,7 @@ class AsyncEngineCore:
                                                      self._result_q, mp_task_q, self.gpu_ids)
         self.task_queue = ep.ProcessTaskQueue(mp_task_q, self._router, affinity_qs, self.prefix_affinity)
         self._router.start()
-        self._monitor = ep.LivenessMonitor(self.workers, self._result_q, lambda: self.is_shutdown)
+        self._monitor = ep.LivenessMonitor(self.workers, self._router, lambda: self.is_shutdown)
         self._monitor.start()
 
     def _send_arena_free(self, worker_id: str, row: int) -> None:
@@ -175,8 +181,9 @@ class AsyncEngineCore:
                 w.control_q.put({"type": "arena_free", "row": int(row)})
 
     def _on_process_worker_exit(self, worker_id: str, kind: str) -> None:
-        """Router thread: a worker process reported an error or ended -- by its own message, or, for a hard exit (HIP abort,
-        segmentation fault, kill), by the LivenessMonitor that watches the process sentinels.  Its requests are completed as
+        """A worker process reported an error or ended -- by its own message (router thread), or, for a hard exit (HIP abort,
+        segmentation fault, kill), through the LivenessMonitor that watches the process sentinels (its thread); the router lets one
+        such call run at a time (ResultRouter._worker_gone).  Its requests are completed as
         aborted (its own loop does that when it can), and so are the queued ones when no worker is left."""
         if self.is_shutdown or self._router is None:
             return
@@ -441,7 +448,8 @@ class AsyncEngineCore:
                 if w.process.is_alive():
                     w.process.terminate()
             self._result_q.put(None)
-            self._router.join(timeout=5)
+            self._result_q.cancel_join_thread()      # a worker that died holding the queue's write lock leaves this put (and the router's
+            self._router.join(timeout=5)             # read) blocked for good: neither may hold up the interpreter's exit
             return
         for _ in range(max(1, len(self.workers))):       # every worker consumes one shutdown event
             self.event_queue.put_nowait({"type": "shutdown"})

@@ -357,6 +357,7 @@ class ResultRouter(threading.Thread):
         self._tasks: Dict[str, Task] = {}
         self.owner: Dict[str, str] = {}                 # task id -> worker id, once pulled
         self._lock = threading.Lock()
+        self._exit_lock = threading.Lock()              # one worker-exit handling at a time (_worker_gone)
         self.remote_arena = remote_arena
         self._pinned: Dict[str, RemoteStateRef] = {}    # task id -> the arena row its request starts from, until installed
         self.installs = {"local": 0, "peer": 0}         # arena rows installed by their own worker / by another one (IPC)
@@ -390,12 +391,35 @@ class ResultRouter(threading.Thread):
             return [t for tid, t in self._tasks.items() if tid not in self.owner]
 
     def finish_aborted(self, task: Task) -> None:
-        task.request_status = RequestStatus.FINISHED_ABORTED
-        self._unpin(task.task_id)
+        """Complete a registered request as aborted -- once: whoever takes it out of the table (this call, from either thread, or
+        run() on the worker's own "task_completed") sends its last message; a second caller finds it gone and sends nothing."""
         with self._lock:
-            self._tasks.pop(task.task_id, None)
+            known = self._tasks.pop(task.task_id, None) is not None
             self.owner.pop(task.task_id, None)
-        task.output_queue.put_nowait(("task_completed", task))
+        self._unpin(task.task_id)
+        if known:
+            task.request_status = RequestStatus.FINISHED_ABORTED
+            task.output_queue.put_nowait(("task_completed", task))
+
+    def _worker_gone(self, wid: str, kind: str) -> None:
+        """A worker's end, reported by its own message (router thread) or by the liveness monitor (its thread): ONE at a time.  The
+        engine's handler reads the worker's tasks, marks its arena dead and drains its queue -- check-then-act sequences that two
+        reports of the same end (a worker that says "worker_error" and then ends) must not interleave."""
+        with self._exit_lock:
+            self._on_exit(wid, kind)
+        with self.peers_released_cv:                    # (a worker that is gone holds no handles either)
+            self.peers_released.add(wid)
+            self.peers_released_cv.notify_all()
+
+    def worker_ended(self, wid: str, error: str) -> None:
+        """LivenessMonitor's thread: the process of `wid` has ended without a goodbye.  Handled HERE, not by a message through the
+        result queue: a process that dies while its queue feeder thread holds the queue's write lock, or half-way through a
+        message, leaves that queue closed to every other writer and its reader blocked -- the monitor's own messages would never
+        arrive and the worker's clients would wait forever.  (A worker ends like that whenever a HIP abort, a kill or os._exit takes
+        the process while it is streaming tokens: its feeder thread holds the lock for the length of every message.)  Serialised with
+        the router thread's own handling of a worker's goodbye by ``_worker_gone``; a request is completed once (``finish_aborted``)."""
+        self._worker_gone(wid, "worker_error")
+        self._events.put_nowait((wid, "worker_error", {"error": error}))
 
     def run(self):
         while True:
@@ -411,10 +435,7 @@ class ResultRouter(threading.Thread):
                         self.peers_released_cv.notify_all()
                     continue
                 if kind in ("worker_exit", "worker_error"):
-                    self._on_exit(wid, kind)
-                    with self.peers_released_cv:        # (a worker that is gone holds no handles either)
-                        self.peers_released.add(wid)
-                        self.peers_released_cv.notify_all()
+                    self._worker_gone(wid, kind)
                 if kind != "worker_exit":
                     self._events.put_nowait(msg)
                 continue
@@ -464,13 +485,13 @@ class LivenessMonitor(threading.Thread):
     """Engine-side watch over the worker PROCESSES.  A worker that ends without its own goodbye -- a HIP abort or a
     segmentation fault on a GPU fault, an out-of-memory kill, os._exit -- never sends "worker_exit" (that message comes from a
     `finally` of the worker's Python code); its clients would wait forever and init() would sit out its 300-s load timeout.
-    This thread waits on the processes' sentinels and, for a process that ended while the engine is not shutting down, posts a
-    "worker_error" event (init() fails fast on it) and "worker_exit" (the router completes the worker's requests as aborted).
-    Nothing is restarted."""
+    This thread waits on the processes' sentinels and, for a process that ended while the engine is not shutting down, tells the
+    router directly (ResultRouter.worker_ended): a "worker_error" event (init() fails fast on it), and the worker's requests are
+    completed as aborted.  Nothing is restarted."""
 
-    def __init__(self, handles, result_q, is_shutdown: Callable[[], bool]):
+    def __init__(self, handles, router: "ResultRouter", is_shutdown: Callable[[], bool]):
         super().__init__(daemon=True, name="chirrup:liveness")
-        self._handles, self._q, self._is_shutdown = list(handles), result_q, is_shutdown
+        self._handles, self._router, self._is_shutdown = list(handles), router, is_shutdown
         self._stop_r, self._stop_w = mp.Pipe(duplex=False)
 
     def stop(self):
@@ -489,10 +510,9 @@ class LivenessMonitor(threading.Thread):
                 h = live.pop(s_)
                 if self._is_shutdown():
                     continue
-                code = h.process.exitcode
-                self._q.put(("__worker_event__", (h.worker_id, "worker_error",
-                                                  {"error": f"worker process ended unexpectedly (exit code {code})"})))
-                self._q.put(("__worker_event__", (h.worker_id, "worker_exit", {})))
+                h.process.join(timeout=5.0)      # the sentinel closes a moment before the process can be reaped: wait for its exit code,
+                #                                  so that whoever hears of the end finds is_alive() False
+                self._router.worker_ended(h.worker_id, f"worker process ended unexpectedly (exit code {h.process.exitcode})")
 
 
 def spawn_workers(worker_num: int, model_config: ModelLoadConfig, batch_size: int, worker_factory, worker_kwargs, result_q, task_q,

@@ -112,6 +112,8 @@ SIGNATURES = {
     "mxfp4_gemm_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "mxfp4_gemm": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mxfp4_gemm_partial": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _f32p, _vp]),
+    "rwkv7_state_pack": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "rwkv7_state_unpack": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 

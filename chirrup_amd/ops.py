@@ -15,11 +15,13 @@ Differences from the reference, all on the safe side:
 """
 from typing import Optional
 
+import contextlib
 import ctypes
 
 import torch
 
 from . import lib as _lib
+from .quant import MXINT8_HEAD_BYTES, pack_state_mxint8, unpack_state_mxint8
 
 HEAD_SIZE = 64
 
@@ -664,6 +666,53 @@ def fork_states(pool, groups) -> None:
     rc = _lib.load().rwkv7_fork_states(n, L, S, C, C // HEAD_SIZE, _ptr(dev), _ptr(dev[n:]), _ptr(dev[2 * n + 1:]), _ptr(shift), _ptr(wkv),
                                        _ptr(elapsed), _stream())
     _lib.check(rc, "rwkv7_fork_states")
+
+
+def _chk_state_codec(what: str, pool_wkv, slot: int, packed_row):
+    """Host checks of state_pack / state_unpack -> (L, S, H)."""
+    if pool_wkv.dim() != 5 or tuple(pool_wkv.shape[3:]) != (HEAD_SIZE, HEAD_SIZE) or pool_wkv.dtype != torch.float16:
+        raise _lib.ChirrupAmdError(f"{what}: expected the table wkv binary16 [L, S, H, 64, 64], got {pool_wkv.dtype} {tuple(pool_wkv.shape)}")
+    L, S, H = pool_wkv.shape[:3]
+    if packed_row.dtype != torch.uint8 or tuple(packed_row.shape) != (L, H, MXINT8_HEAD_BYTES):
+        raise _lib.ChirrupAmdError(f"{what}: expected a packed row uint8 {(L, H, MXINT8_HEAD_BYTES)}, got {packed_row.dtype} "
+                                   f"{tuple(packed_row.shape)}")
+    if not pool_wkv.is_contiguous() or not packed_row.is_contiguous():
+        raise _lib.ChirrupAmdError(f"{what}: the table and the packed row must be contiguous")
+    if pool_wkv.device != packed_row.device:
+        raise _lib.ChirrupAmdError(f"{what}: the table is on {pool_wkv.device}, the packed row on {packed_row.device}")
+    if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < S:
+        raise _lib.ChirrupAmdError(f"{what}: slot {slot!r} is outside [0, {S})")
+    return L, S, H
+
+
+def _on_device(dev):
+    """The launch goes to the current stream OF THE TABLE'S DEVICE (an arena may be filled from a thread whose current device is another)."""
+    return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+def state_pack(pool_wkv, slot: int, packed_row) -> None:
+    """MXINT8 prefix-state arena: the head states of slot `slot` of the worker's table wkv binary16 [L, S, H, 64, 64] -> packed_row
+    uint8 [L, H, 4224] (include/chirrup_amd.h: rwkv7_state_pack; the format: quant.pack_state_mxint8, which CPU tensors take).  One
+    launch on the current stream; only `packed_row` is written."""
+    L, S, H = _chk_state_codec("state_pack", pool_wkv, slot, packed_row)
+    if not pool_wkv.is_cuda:
+        packed_row.copy_(pack_state_mxint8(pool_wkv[:, slot]))
+        return
+    with _on_device(pool_wkv.device):
+        rc = _lib.load().rwkv7_state_pack(L, S, H, slot, _ptr(pool_wkv), _ptr(packed_row), _stream())
+    _lib.check(rc, "rwkv7_state_pack")
+
+
+def state_unpack(packed_row, pool_wkv, slot: int) -> None:
+    """The inverse: packed_row uint8 [L, H, 4224] -> slot `slot` of wkv binary16 [L, S, H, 64, 64], exactly (rwkv7_state_unpack;
+    quant.unpack_state_mxint8 for CPU tensors).  Only that slot is written."""
+    L, S, H = _chk_state_codec("state_unpack", pool_wkv, slot, packed_row)
+    if not pool_wkv.is_cuda:
+        pool_wkv[:, slot].copy_(unpack_state_mxint8(packed_row))
+        return
+    with _on_device(pool_wkv.device):
+        rc = _lib.load().rwkv7_state_unpack(L, S, H, slot, _ptr(packed_row), _ptr(pool_wkv), _stream())
+    _lib.check(rc, "rwkv7_state_unpack")
 
 
 class TiledWeight:

@@ -1,4 +1,5 @@
-"""Weight quantisation, host side: mm8 (w8a16, below) and MXFP4 (w4a16, second half of the file).
+"""Quantisation, host side: the weight formats mm8 (w8a16, below) and MXFP4 (w4a16, second part of the file), and the MXINT8 codec of
+the prefix-state arena's head states (last part).
 
 Restates the reference's quantize_weight (scripts/test_mm8/benchmark.py:54-85, the rwkv pip package's
 scheme): for w [N_in, M_out] subtract column minima mx and row minima my (order depends on the
@@ -138,3 +139,63 @@ def untile_mxfp4(flat: torch.Tensor, m_out: int, n_in: int) -> Mxfp4Weight:
     codes = img[..., :4096].reshape(G, B, 128, 4, 2, 4).permute(0, 2, 1, 4, 3, 5).reshape(m_out, n_in // 2)     # [g, r, b, s, q, j]
     scales = img[..., 4096:].reshape(G, B, 128, 2).permute(0, 2, 1, 3).reshape(m_out, n_in // 32)
     return Mxfp4Weight(codes.contiguous(), scales.contiguous())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MXINT8 head states of the prefix-state arena (include/chirrup_amd.h: rwkv7_state_pack; DESIGN.md "MXINT8 prefix-state arena")
+
+MXINT8_BLOCK = 32
+MXINT8_E_MIN, MXINT8_E_MAX = -18, 15             # 2^(e-6) times a code of -127..127 is +-0 or a binary16 number
+MXINT8_HEAD_ELEMS = 64 * 64
+MXINT8_HEAD_BYTES = MXINT8_HEAD_ELEMS + MXINT8_HEAD_ELEMS // MXINT8_BLOCK     # 4096 codes, then 128 scale bytes
+MXINT8_NAN_SCALE = 0xFF
+
+
+def mxint8_block_exponent(amax16: torch.Tensor) -> torch.Tensor:
+    """Block exponents (int32) of non-negative finite binary16 block maxima: the smallest e with amax <= 127 * 2^(e-6), held to
+    [-18, 15].  From the bits alone: binary32 holds every binary16 value exactly and normalised, amax = f * 2^p with 1 <= f < 2, and
+    f <= 127/64 is a comparison of the 23 fraction bits with 63/64.  An all-zero block takes -18."""
+    b = amax16.to(torch.float16).to(torch.float32).view(torch.int32)
+    e = (b >> 23) - 127 + ((b & 0x7FFFFF) > 0x7E0000).to(torch.int32)
+    return torch.where(b == 0, torch.full_like(e, MXINT8_E_MIN), e).clamp(MXINT8_E_MIN, MXINT8_E_MAX)
+
+
+def pack_state_mxint8(wkv: torch.Tensor) -> torch.Tensor:
+    """Head states binary16 [..., 64, 64] -> uint8 [..., 4224]: per head 4096 int8 codes in element order, then 128 E8M0 scale bytes,
+    one per block of 32 consecutive elements.  scale byte = e + 127 (mxint8_block_exponent); code = clamp(RNE(x * 2^(6-e)), -127,
+    127) in two's complement (-128 is never written, -0 gives 0).  A block with a NaN or an infinity: scale byte 0xFF, codes 0.
+    Deterministic and exact (the scaling is by a power of two, the rounding torch.round's ties-to-even); on the tensor's device."""
+    if wkv.dtype != torch.float16 or wkv.dim() < 2 or tuple(wkv.shape[-2:]) != (64, 64):
+        raise ValueError(f"pack_state_mxint8: expected binary16 [..., 64, 64], got {wkv.dtype} {tuple(wkv.shape)}")
+    lead = tuple(wkv.shape[:-2])
+    x = wkv.contiguous().reshape(lead + (MXINT8_HEAD_ELEMS // MXINT8_BLOCK, MXINT8_BLOCK))
+    mag = (x.view(torch.int16).to(torch.int32) & 0x7FFF).amax(-1)                  # binary16 magnitudes order like their bits
+    bad = mag >= 0x7C00
+    e = mxint8_block_exponent(torch.where(bad, torch.zeros_like(mag), mag).to(torch.int16).view(torch.float16))
+    y = torch.ldexp(x.to(torch.float32), (6 - e).unsqueeze(-1).expand(x.shape))   # exact
+    codes = torch.round(y).clamp(-127, 127).to(torch.int8)
+    codes = torch.where(bad.unsqueeze(-1), torch.zeros_like(codes), codes).view(torch.uint8)
+    scales = torch.where(bad, torch.full_like(e, MXINT8_NAN_SCALE), e + 127).to(torch.uint8)
+    return torch.cat([codes.reshape(lead + (MXINT8_HEAD_ELEMS,)), scales], -1).contiguous()
+
+
+def unpack_state_mxint8(packed: torch.Tensor) -> torch.Tensor:
+    """uint8 [..., 4224] -> binary16 [..., 64, 64]: code * 2^(scale - 133), which is +-0 or a binary16 number for every code and every
+    scale byte 109..142 -- nothing is rounded.  Scale byte 0xFF gives 32 quiet NaNs (0x7E00); other bytes are held to 109..142."""
+    if packed.dtype != torch.uint8 or packed.dim() < 1 or packed.shape[-1] != MXINT8_HEAD_BYTES:
+        raise ValueError(f"unpack_state_mxint8: expected uint8 [..., {MXINT8_HEAD_BYTES}], got {packed.dtype} {tuple(packed.shape)}")
+    lead = tuple(packed.shape[:-1])
+    nb = MXINT8_HEAD_ELEMS // MXINT8_BLOCK
+    codes = packed[..., :MXINT8_HEAD_ELEMS].contiguous().view(torch.int8).reshape(lead + (nb, MXINT8_BLOCK)).to(torch.float32)
+    sb = packed[..., MXINT8_HEAD_ELEMS:].to(torch.int32)
+    e = sb.clamp(127 + MXINT8_E_MIN, 127 + MXINT8_E_MAX) - 127
+    v = torch.ldexp(codes, (e - 6).unsqueeze(-1).expand(codes.shape))
+    out = v.to(torch.float16)
+    nan = torch.full((), 0x7E00, dtype=torch.int16, device=packed.device).view(torch.float16)
+    out = torch.where((sb == MXINT8_NAN_SCALE).unsqueeze(-1), nan, out)
+    return out.reshape(lead + (64, 64))
+
+
+def roundtrip_state_mxint8(wkv: torch.Tensor) -> torch.Tensor:
+    """S~ = unpack(pack(S)): what a packed arena hands back for the head states S."""
+    return unpack_state_mxint8(pack_state_mxint8(wkv))

@@ -213,8 +213,8 @@ class PeerArenas:
 
     def install(self, worker_id: str, row: int, pool: Sequence[torch.Tensor], slot: int) -> None:
         """Arena row -> slot of this worker's state tables: one strided device copy per tensor (another process's memory on
-        the same GPU, or a peer copy from another GPU)."""
+        the same GPU, or a peer copy from another GPU); a packed arena (uint8 ``wkv``) is unpacked: state_cache.install_row."""
+        from .state_cache import install_row
+
         shift, wkv, elapsed = self.tensors_of(worker_id)
-        pool[0][:, :, slot, :].copy_(shift[row], non_blocking=True)
-        pool[1][:, slot].copy_(wkv[row], non_blocking=True)
-        pool[2][slot: slot + 1].copy_(elapsed[row: row + 1], non_blocking=True)
+        install_row(shift, wkv, elapsed, row, pool, slot)

@@ -22,6 +22,10 @@ Two parts:
   (``ArenaRef.install_into``) and unpins it.  A row that is evicted while a hit on it is still queued is only returned
   to the free list when the last pin is gone.  4096 rows of a 13.3B state (33 MB) are 135 GB.
   ``SimpleStateCache(max_size, arena=HbmStateArena(...))`` stores its states there.
+  ``HbmStateArena(..., wkv_format="mxint8")`` keeps the head states packed (OCP Microscaling INT8, quant.pack_state_mxint8:
+  4224 bytes per head instead of 8192, so 4096 such rows are 72 GB): rows are packed on the way in and unpacked on the way out
+  by one kernel launch each (ops.state_pack / state_unpack), and a hit continues from the codec's round trip of the exported
+  state (DESIGN.md "MXINT8 prefix-state arena").
 """
 import asyncio
 import threading
@@ -29,6 +33,27 @@ from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
+
+from . import ops
+
+
+WKV_FORMATS = (None, "mxint8")
+
+
+def install_row(shift: torch.Tensor, wkv: torch.Tensor, elapsed: torch.Tensor, row: int, pool: Sequence[torch.Tensor], slot: int) -> None:
+    """Row `row` of an arena's three tensors -> slot `slot` of a worker's state tables, on the current stream.  A plain arena: one
+    strided copy per tensor.  A packed one (``wkv`` is uint8, MXINT8): ``ops.state_unpack`` reads the row where it lies -- this
+    process's arena, or another process's on the same device, opened through its IPC handle; a row on ANOTHER device is first copied,
+    still packed, into a local staging buffer (half the bytes over xGMI) and unpacked from there."""
+    pool[0][:, :, slot, :].copy_(shift[row], non_blocking=True)
+    if wkv.dtype == torch.uint8:
+        packed = wkv[row]
+        if packed.device != pool[1].device:
+            packed = torch.empty_like(packed, device=pool[1].device).copy_(packed, non_blocking=True)
+        ops.state_unpack(packed, pool[1], int(slot))
+    else:
+        pool[1][:, slot].copy_(wkv[row], non_blocking=True)
+    pool[2][slot: slot + 1].copy_(elapsed[row: row + 1], non_blocking=True)
 
 
 class ArenaRef:
@@ -41,12 +66,11 @@ class ArenaRef:
 
     def install_into(self, pool: Sequence[torch.Tensor], slot: int) -> None:
         """One strided device-to-device copy per state tensor: arena row -> slot `slot` of the worker's tables
-        [L,2,n,C], [L,n,H,64,64], [n] (works across devices: a peer copy over xGMI)."""
+        [L,2,n,C], [L,n,H,64,64], [n] (works across devices: a peer copy over xGMI); a packed arena's head states are unpacked
+        by one kernel launch instead (install_row)."""
         a = self.arena
         a.wait_ready(self.row)               # the export into the row may still be queued on ANOTHER worker's stream
-        pool[0][:, :, slot, :].copy_(a.shift[self.row], non_blocking=True)
-        pool[1][:, slot].copy_(a.wkv[self.row], non_blocking=True)
-        pool[2][slot: slot + 1].copy_(a.elapsed[self.row: self.row + 1], non_blocking=True)
+        install_row(a.shift, a.wkv, a.elapsed, self.row, pool, slot)
 
     def tensors(self) -> List[torch.Tensor]:
         """Copies in the reference's exported layout [L,2,1,C], [L,1,H,64,64], [1] (for consumers that want tensors)."""
@@ -68,14 +92,27 @@ class HbmStateArena:
     """Preallocated pool of ``capacity`` RWKV-7 request states on one device."""
 
     def __init__(self, n_layer: int, n_embd: int, capacity: int, device, head_size: int = 64, dtype=torch.float16,
-                 wkv_shape=None, wkv_dtype=None):
+                 wkv_shape=None, wkv_dtype=None, wkv_format=None):
         """wkv_shape / wkv_dtype: per-layer shape and dtype of state[1] when they are not the model's [H, 64, 64] binary16
-        (host-logic tests with a fake backend)."""
+        (host-logic tests with a fake backend).  wkv_format="mxint8": the head states are kept packed (quant.pack_state_mxint8:
+        4224 bytes per head instead of 8192); ``wkv`` is then uint8 [capacity, L, H, 4224], rows are packed on the way in and
+        unpacked on the way out, and what comes out is the codec's round trip of what went in.  state[0] and state[2] stay as
+        they are."""
         if capacity <= 0:
             raise ValueError("capacity must be positive")
+        if wkv_format not in WKV_FORMATS:
+            raise ValueError(f"wkv_format must be one of {WKV_FORMATS}, got {wkv_format!r}")
         self.n_layer, self.n_embd, self.capacity = n_layer, n_embd, capacity
         H = n_embd // head_size
         wkv_shape = tuple(wkv_shape) if wkv_shape is not None else (H, head_size, head_size)
+        self.wkv_format = wkv_format
+        if wkv_format == "mxint8":
+            from .quant import MXINT8_HEAD_BYTES
+
+            if (wkv_dtype or dtype) != torch.float16 or len(wkv_shape) != 3 or wkv_shape[1:] != (64, 64):
+                raise ValueError(f"wkv_format='mxint8' needs binary16 [H, 64, 64] head states, not {wkv_dtype or dtype} {wkv_shape}")
+            self._wkv_state_shape = wkv_shape
+            wkv_shape, wkv_dtype = (wkv_shape[0], MXINT8_HEAD_BYTES), torch.uint8
         self.shift = torch.empty((capacity, n_layer, 2, n_embd), dtype=dtype, device=device)            # state[0] rows
         self.wkv = torch.empty((capacity, n_layer) + wkv_shape, dtype=wkv_dtype or dtype, device=device)  # state[1] rows
         self.elapsed = torch.zeros((capacity,), dtype=torch.int32, device=device)                       # state[2]
@@ -89,13 +126,15 @@ class HbmStateArena:
         self._lock = threading.Lock()  # the cache runs on the engine's thread, installs on the worker's
 
     @classmethod
-    def for_model(cls, model, capacity: int):
+    def for_model(cls, model, capacity: int, wkv_format=None):
         """Geometry from a chirrup_amd.rwkv7.RWKV_x070 (n_layer, n_embd, head_size, device)."""
-        return cls(model.n_layer, model.n_embd, capacity, model.device, head_size=model.head_size)
+        return cls(model.n_layer, model.n_embd, capacity, model.device, head_size=model.head_size, wkv_format=wkv_format)
 
     @property
     def bytes_per_state(self) -> int:
-        return (self.shift[0].numel() + self.wkv[0].numel()) * self.shift.element_size() + 4
+        if self.wkv_format is None:
+            return (self.shift[0].numel() + self.wkv[0].numel()) * self.shift.element_size() + 4
+        return self.shift[0].numel() * self.shift.element_size() + self.wkv[0].numel() + 4        # the packed size: uint8 head states
 
     @property
     def free_rows(self) -> int:
@@ -112,9 +151,17 @@ class HbmStateArena:
         s0, s1, s2 = state
         if tuple(s0.shape) != (self.n_layer, 2, 1, self.n_embd) or s1.shape[0] != self.n_layer or s1.shape[1] != 1:
             raise ValueError(f"state shapes {tuple(s0.shape)}, {tuple(s1.shape)} do not match the arena")
+        if self.wkv_format is not None and (s1.dtype != torch.float16 or tuple(s1.shape[2:]) != self._wkv_state_shape):
+            raise ValueError(f"state[1] {s1.dtype} {tuple(s1.shape)} does not match the packed arena")
         row = self._take_row()
         self.shift[row].copy_(s0[:, :, 0, :], non_blocking=True)
-        self.wkv[row].copy_(s1[:, 0], non_blocking=True)
+        if self.wkv_format is None:
+            self.wkv[row].copy_(s1[:, 0], non_blocking=True)
+        else:
+            # the tensors as a one-slot table [L, 1, H, 64, 64] on the arena's device: a binary16 copy of the state per call when the
+            # caller's tensors are elsewhere or strided.  This is the cold path (tensors handed in by callers); a worker's export
+            # goes through export_slot, which packs straight out of its table.
+            ops.state_pack(s1.to(self.wkv.device, non_blocking=True).contiguous(), 0, self.wkv[row])
         self.elapsed[row: row + 1].copy_(s2.reshape(1), non_blocking=True)
         self._mark_filled(row)
         return row
@@ -145,9 +192,14 @@ class HbmStateArena:
         ``SimpleStateCache.cache`` (which takes the row over) or release it."""
         if tuple(pool[0].shape[:2]) != (self.n_layer, 2) or pool[0].shape[3] != self.n_embd:
             raise ValueError("state tables do not match the arena")
+        if self.wkv_format is not None and (pool[1].dtype != torch.float16 or tuple(pool[1].shape[2:]) != self._wkv_state_shape):
+            raise ValueError("state tables do not match the packed arena")
         row = self._take_row()
         self.shift[row].copy_(pool[0][:, :, slot, :], non_blocking=True)
-        self.wkv[row].copy_(pool[1][:, slot], non_blocking=True)
+        if self.wkv_format is None:
+            self.wkv[row].copy_(pool[1][:, slot], non_blocking=True)
+        else:
+            ops.state_pack(pool[1], int(slot), self.wkv[row])       # slot -> packed row, one launch on the same stream as the copies
         self.elapsed[row: row + 1].copy_(pool[2][slot: slot + 1], non_blocking=True)
         self._mark_filled(row)
         with self._lock:
@@ -178,7 +230,12 @@ class HbmStateArena:
     def get(self, row: int) -> List[torch.Tensor]:
         """A device copy of row ``row`` in the layout the reference exports ([L,2,1,C], [L,1,H,64,64], [1])."""
         self.wait_ready(row)
-        return [self.shift[row].unsqueeze(2).clone(), self.wkv[row].unsqueeze(1).clone(), self.elapsed[row: row + 1].clone()]
+        if self.wkv_format is None:
+            wkv = self.wkv[row].unsqueeze(1).clone()
+        else:
+            wkv = torch.empty((self.n_layer, 1) + self._wkv_state_shape, dtype=torch.float16, device=self.wkv.device)
+            ops.state_unpack(self.wkv[row], wkv, 0)
+        return [self.shift[row].unsqueeze(2).clone(), wkv, self.elapsed[row: row + 1].clone()]
 
     def release(self, row: int) -> None:
         """The owner (the cache) gives the row up; it is reused once no hit holds it any more."""
@@ -387,4 +444,4 @@ class SimpleStateCache:
         return None
 
 
-__all__ = ["SimpleStateCache", "HbmStateArena", "ArenaRef", "TrieNode"]
+__all__ = ["SimpleStateCache", "HbmStateArena", "ArenaRef", "TrieNode", "install_row"]

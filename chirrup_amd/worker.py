@@ -237,7 +237,7 @@ class Worker:
                  master_event_queue: queue.Queue, worker_event_queue: Optional[queue.Queue], batch_size: int = 32,
                  model=None, tokenizer=None, penalize_argmax=None, state_cache_device=None, run_ahead: bool = True,
                  state_arena=None, state_arena_rows: int = 0, peer_arenas=None, guide_pool_rows: int = 16384,
-                 grammar_pool_rows: int = 2048):
+                 grammar_pool_rows: int = 2048, state_arena_format: Optional[str] = None):
         self.worker_id, self.gpu_id, self.model_config = worker_id, gpu_id, model_config
         self.task_queue, self.master_event_queue, self.worker_event_queue = task_queue, master_event_queue, worker_event_queue
         self.real_state_size = batch_size
@@ -261,6 +261,8 @@ class Worker:
         # process mode: build an arena of this many rows on this worker's own device (after the model has loaded) and publish it
         # to the other worker processes (remote_arena.PeerArenas): prefix states then never leave HBM
         self.state_arena_rows, self.peer_arenas = int(state_arena_rows), peer_arenas
+        # how that arena keeps state[1]: None = binary16 as in the slot table, "mxint8" = packed (HbmStateArena(wkv_format=))
+        self.state_arena_format = state_arena_format
         self._pending_installs = []                   # (event, task id): copies out of ANOTHER worker's arena still in flight
         self.run_ahead = run_ahead
         self.on_fatal = None                          # callable(worker, exception), set by the engine
@@ -375,7 +377,7 @@ class Worker:
 
             s0, s1 = self.batch_state[0], self.batch_state[1]
             self.state_arena = HbmStateArena(s0.shape[0], s0.shape[3], self.state_arena_rows, dev, dtype=s0.dtype,
-                                             wkv_shape=s1.shape[2:], wkv_dtype=s1.dtype)
+                                             wkv_shape=s1.shape[2:], wkv_dtype=s1.dtype, wkv_format=self.state_arena_format)
             if hasattr(self.task_queue, "arena"):
                 self.task_queue.arena = self.state_arena          # exports into it leave this process as row addresses
             if self.peer_arenas is not None:

@@ -726,6 +726,23 @@ int mxfp4_gemm(int M, int N, int K, const void *X, int ldx, const void *Wt, void
                void *stream);
 int mxfp4_gemm_partial(int M, int N, int K, const void *X, int ldx, const void *Wt, int splits, float *partials, void *stream);
 
+/*
+ * MXINT8 prefix-state arena, csrc/state_codec.hip: the head states of ONE slot of the worker's table wkv binary16 [L][S][H][64][64]
+ * <-> a packed arena row uint8 [L][H][CHIRRUP_MXINT8_HEAD_BYTES].  A head is 4096 int8 codes in element order, then 128 E8M0 scale
+ * bytes, one per block of 32 consecutive elements (a 64-element row is two blocks).  scale byte = e + 127, e the smallest integer
+ * with amax <= 127 * 2^(e-6), held to [-18, 15] (an all-zero block: -18), from the bits of amax: with amax = f * 2^p, 1 <= f < 2,
+ * e = p when f <= 127/64, else p + 1.  code = clamp(RNE(x * 2^(6-e)), -127, 127), two's complement, never -128; -0 gives code 0.
+ * value = code * 2^(e-6): +-0 or a binary16 number for every code and exponent, so unpacking rounds nothing.  For a block not held
+ * at e = 15, |x - value| <= 2^(e-7) < amax / 127; |x| > 65024 saturates to +-65024.  A block holding a NaN or an infinity takes
+ * scale byte 0xFF and codes 0; scale byte 0xFF unpacks to 32 quiet NaNs (0x7E00).  Other scale bytes outside 109..142 unpack as
+ * the nearest of the two.
+ * Grid (H, L), 16-byte loads and stores, no LDS; 8192 + 4224 bytes per head.  0 <= slot < S; wkv and packed 16-byte aligned.  Only
+ * slot `slot` is read (pack) or written (unpack); the packed row is written (pack) or read (unpack) in full.
+ */
+#define CHIRRUP_MXINT8_HEAD_BYTES 4224
+int rwkv7_state_pack(int L, int S, int H, int slot, const void *wkv, void *packed, void *stream);
+int rwkv7_state_unpack(int L, int S, int H, int slot, const void *packed, void *wkv, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

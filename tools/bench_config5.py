@@ -10,7 +10,11 @@ chirrup/worker.py:421-435, :591-597).
   checks   every hit request generates exactly the ids of its uncached run; the arena holds >= 2048 resident rows.
   reports  decode iteration time of the 64-row mix, prefill + admission time of hits vs misses, hit-install cost.
 
-usage: python tools/bench_config5.py [rows=2048] [prompt_len=384] [new_tokens=48] [out.txt]
+usage: python tools/bench_config5.py [--arena-format mxint8] [rows=2048] [prompt_len=384] [new_tokens=48] [out.txt]
+
+--arena-format mxint8 keeps the arena's head states packed (HbmStateArena(wkv_format="mxint8"), DESIGN.md "MXINT8 prefix-state
+arena"): a hit then continues from the codec's round trip of the exported state, so its ids are COMPARED with the uncached run's
+and the number of requests that differ is reported, not asserted.  Default: the plain binary16 arena.
 """
 import os
 import queue
@@ -26,6 +30,13 @@ from chirrup_amd.state_cache import ArenaRef, HbmStateArena, SimpleStateCache
 from chirrup_amd.synth import CONFIGS, make_state_dict
 from chirrup_amd.worker import Worker
 
+arena_format = None
+if "--arena-format" in sys.argv:
+    k = sys.argv.index("--arena-format")
+    if k + 1 >= len(sys.argv) or sys.argv[k + 1] not in ("mxint8",):
+        sys.exit("--arena-format takes one value: mxint8 (leave the option out for the plain binary16 arena)")
+    arena_format = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
 plen = int(sys.argv[2]) if len(sys.argv) > 2 else 384
 new = int(sys.argv[3]) if len(sys.argv) > 3 else 48
@@ -46,9 +57,9 @@ zd = make_state_dict(L, C, 65536, seed=42, device=dev)
 model = RWKV_x070(model_args("synthetic"), state_dict=zd, device=dev)
 del zd
 torch.cuda.empty_cache()
-arena = HbmStateArena.for_model(model, capacity=rows + bsz)          # cached rows + one per request in flight
+arena = HbmStateArena.for_model(model, capacity=rows + bsz, wkv_format=arena_format)          # cached rows + one per request in flight
 cache = SimpleStateCache(max_size=rows, arena=arena)
-say(f"# config 5 on one MI355X: RWKV7-g1 {name} (L={L}, C={C}), bsz {bsz}, prefix cache of {rows} rows x {arena.bytes_per_state / 1e6:.2f} MB "
+say(f"# config 5 on one MI355X: RWKV7-g1 {name} (L={L}, C={C}), bsz {bsz}, arena format {arena_format or 'binary16'}, prefix cache of {rows} rows x {arena.bytes_per_state / 1e6:.2f} MB "
     f"= {rows * arena.bytes_per_state / 1e9:.1f} GB resident in HBM (arena {arena.capacity} rows); model + arena ready in {time.perf_counter() - t0:.0f} s; "
     f"HBM in use {torch.cuda.memory_allocated() / 1e9:.1f} GB")
 
@@ -135,9 +146,13 @@ misses = [mk(p) for p in prompts[32:]]
 mix = [t for pair in zip(hits, misses) for t in pair]
 wallB, medB = drain(mix, "phase B (64 requests, 32 hits + 32 misses)")
 bad = [i for i, (a, b) in enumerate(zip(hits, tA)) if ids_of(a) != ids_of(b)]
-assert not bad, f"hit requests {bad} diverge from their uncached run"
 assert all(len(ids_of(t)) == new for t in mix)
-say(f"ids of all 32 hit requests equal their uncached run ({new} greedy tokens each); all pins released: free arena rows {arena.free_rows}")
+if arena_format is None:
+    assert not bad, f"hit requests {bad} diverge from their uncached run"
+    say(f"ids of all 32 hit requests equal their uncached run ({new} greedy tokens each); all pins released: free arena rows {arena.free_rows}")
+else:                      # a packed hit continues from the rounded state (synthetic weights: says nothing about a trained model)
+    say(f"{len(bad)} of 32 hit requests differ from their uncached run within {new} greedy tokens (packed arena: the state is rounded); "
+        f"all pins released: free arena rows {arena.free_rows}")
 t_hit = sorted(t.output_queue.t_first for t in hits)
 t_miss = sorted(t.output_queue.t_first for t in misses)
 # ---- the same 64 prompts with nothing cached, for the admission / prefill cost the hits avoid
